@@ -15,6 +15,9 @@ touches no GPU: it starts `torch.distributed.run` with N ranks as a CHILD proces
 and exits with its status, so `--gpus N` always means N ranks. A rank whose formed process group
 is not N ranks exits non-zero. Rank 0 prints ONE JSON line; `value` is the whole-job samples/s,
 `rccl_world` the size of the process group that actually formed, `devices` each rank's device.
+A plain run sets up, warms up, times the K steps and prints; `--dump-outputs DIR` then also runs the timed
+path once from the seeded initial state and writes its results (see _dump_outputs) and `--full` adds the secondary
+measurements (the averaging collective timed apart and RCCL's transports, N > 1 only).
 Reference analog: round-robin over every available volunteer, /root/reference/server.py:84-90.
 """
 from __future__ import annotations
@@ -121,7 +124,73 @@ def parse():
     ap.add_argument("--rccl-log", type=int, default=1,
                     help="1: RCCL INIT/P2P log to a file per rank (unless NCCL_DEBUG is set), parsed for the "
                          "transport each connection chose (rccl_transports in the JSON)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, run the timed path once more from the seeded initial state on the "
+                         "first batch, averaging round included, and write what it computed as DIR/<name>.npy: loss, "
+                         "and a fixed seeded sample of the gradient and the AdamW moments (grad, adam_m, adam_v: the "
+                         "informative arrays) and of the updated parameters (after one step ~ p0 - lr sign(g))")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the secondary measurements: with N > 1 ranks, the averaging collective timed "
+                         "apart (avg_* fields; two device synchronisations per round inside the timed steps) and "
+                         "RCCL's connection log parsed for its transports (rccl_transports). At N = 1 there is none")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 21  # elements kept of each flat state vector (8 MB as float32; four vectors: 32 MB)
+DUMP_SEED = 20240229  # of the sample's indices
+
+
+def _dump_outputs(path: str | None, trainer, init, x, y) -> None:
+    """Write what the timed path computes from the run's seeded inputs, as float32 .npy files. The timed steps
+    themselves cannot be compared between runs: a few of the kernels sum with floating-point atomics, whose order
+    changes the last bit of a handful of gradients, and AdamW on bf16 parameters turns that into visibly different
+    parameters within three or four steps (measured: gradient 4e-3 relative L2 apart after 4 steps, 0.7 after 25).
+    So, after the timed steps, the trainer is put back in place to its state before the first step (`init`: the
+    seeded parameters and the optimizer state block; zero moments) and the timed path -- the same captured graph,
+    or the same eager step -- runs once more on the first batch, as the H-th step of its round, so that the
+    averaging round (collective + apply; at N = 1 the anchor copy) is part of what is dumped. That step's loss and
+    one seeded sample (sorted indices, fixed seed) of the fp32 master parameters after it, the gradient and the
+    AdamW moments are written; two runs, or two builds, with the same arguments agree to fp32 rounding (measured
+    at N = 1: loss equal; gradient sample equal or apart in the last bit of an atomically summed bias gradient,
+    2e-6 relative L2; parameters 8e-9 and moments 2e-6, from the clip coefficient's atomic sum of squares). After one step from zero moments the parameters are close to
+    p0 - lr * sign(g) (averaged over the ranks): `grad`, `adam_m` and `adam_v` are the arrays that show a kernel's
+    numerics. Every rank runs the step; `path` is None on the ranks that write nothing."""
+    import numpy as np
+
+    # Everything bench.py's trainer carries from step to step is put back: parameters (bf16 and fp32 master),
+    # anchor, moments, outer momentum, optimizer state block. Deliberately not restored: sync_count and the
+    # timing fields (reporting only; the caller keeps last_sync_ms), the pseudo-gradient `delta` (recomputed by
+    # every round). The trainer here has no BatchNorm buffers and no compressor; one that had would need them
+    # rewound too, so that is refused instead of dumped stale.
+    assert trainer.compressor is None and not trainer.buffers, "--dump-outputs: trainer state that is not rewound"
+    p0, ostate0 = init
+    trainer.flat.param.copy_(p0)
+    trainer.master.copy_(p0)
+    trainer.anchor.copy_(trainer.master)
+    trainer.m.zero_()
+    trainer.v.zero_()
+    if trainer.outer_mom is not None:
+        trainer.outer_mom.zero_()
+    trainer.ostate.copy_(ostate0)
+    trainer.t = trainer.cfg.H - 1  # the step below is the round's last: it ends with the averaging round
+    st = trainer.step(x, y)
+    assert st.synced
+    loss = st.extra["loss_t"]
+    if path is None:
+        return
+    os.makedirs(path, exist_ok=True)
+    n = trainer.flat.numel
+    idx = None
+    if n > DUMP_SAMPLE:
+        g = torch.Generator(device="cpu")
+        g.manual_seed(DUMP_SEED)
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values.to(trainer.device)
+    out = {"loss": loss.detach().reshape(1)}
+    for name, t in (("params", trainer.master), ("grad", trainer.flat.grad), ("adam_m", trainer.m),
+                    ("adam_v", trainer.v)):
+        out[name] = t if idx is None else t.index_select(0, idx)
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def _rccl_log_setup(enable: bool, rank: int) -> str | None:
@@ -161,7 +230,7 @@ def main():
         return 3
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
-    rccl_log = _rccl_log_setup(a.rccl_log and world > 1, rank)
+    rccl_log = _rccl_log_setup(a.full and a.rccl_log and world > 1, rank)
     cuda = torch.cuda.is_available()
     if cuda:
         # one rank per GPU; ranks beyond the GPU count share cards (rehearsal launches only)
@@ -194,6 +263,7 @@ def main():
     model = GPT2(cfg).to(device=device, dtype=torch.bfloat16)
     tcfg = LocalSGDConfig(H=a.H, algo=a.algo)
     trainer = LocalSGDTrainer(model, tcfg, group=group, device=device)
+    init = (trainer.flat.param.clone(), trainer.ostate.clone()) if a.dump_outputs else None
 
     # synthetic token stream: a pool of distinct batches per peer (different shard per rank)
     g = torch.Generator(device=device)
@@ -229,7 +299,8 @@ def main():
 
         allreduce_sum_(torch.zeros_like(trainer.delta), group, a.algo)  # same size as the real round
     sync_all()
-    trainer.time_reduce = world > 1  # the averaging collective timed apart (algbw / busbw below)
+    # --full: the averaging collective timed apart (algbw / busbw below), device-synchronised on both sides
+    trainer.time_reduce = a.full and world > 1
     trainer.reduce_log = []
     t0 = time.perf_counter()
     last = None
@@ -252,11 +323,15 @@ def main():
         devices = [None] * rccl_world
         dist.all_gather_object(devices, dev_desc)
     loss = float(last.extra["loss_t"]) if last is not None else float("nan")
+    if a.dump_outputs:
+        keep, trainer.time_reduce = trainer.last_sync_ms, False  # the extra step leaves the run's figures alone
+        _dump_outputs(a.dump_outputs if rank == 0 else None, trainer, init, *batch(0))
+        trainer.last_sync_ms = keep
     red = trainer.reduce_log
     red_ms = sum(m for m, _ in red) / len(red) if red else None
     red_bytes = red[0][1] if red else trainer.delta.numel() * trainer.delta.element_size()
     transports = {}
-    if world > 1:
+    if a.full and world > 1:
         tr = [None] * world
         dist.all_gather_object(tr, _rccl_transports(rccl_log))
         for d in tr:

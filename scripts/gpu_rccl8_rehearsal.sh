@@ -8,7 +8,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/rccl8
 mkdir -p $O
 L="python -u scripts/rccl_rehearsal_launch.py"
-B="python -u bench.py --steps 8 --warmup 4 --batch 8"
+B="python -u bench.py --full --steps 8 --warmup 4 --batch 8"
 step() {  # name, seconds, command... (ONLY="name1 name2": run just those)
   local name=$1 secs=$2
   shift 2

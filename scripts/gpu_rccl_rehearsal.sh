@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/rccl
 mkdir -p $O
 L="python -u scripts/rccl_rehearsal_launch.py"
-B="python -u bench.py --steps 8 --warmup 4 --batch 4 --seq 256"
+B="python -u bench.py --full --steps 8 --warmup 4 --batch 4 --seq 256"
 step() {  # name, seconds, command...
   local name=$1 secs=$2
   shift 2

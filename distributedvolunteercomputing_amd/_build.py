@@ -127,20 +127,26 @@ def _linked(out: Path, d: str):
 FILE_FLAGS = {"attention.hip": ["-fno-slp-vectorize"]}
 
 
+def kernel_flags(name: str, kernels_dir: Path | None = None) -> list[str]:
+    """The hipcc flags of kernel source `name` (all but -c / -o): shared by build_C and scripts/kernel_isa_diff.py.
+    kernels_dir: where its headers are looked up (default: the package's csrc/kernels)."""
+    kdir = Path(kernels_dir) if kernels_dir is not None else CSRC / "kernels"
+    return [f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast-honor-pragmas",
+            "-munsafe-fp-atomics", f"-I{kdir.parent}", f"-I{kdir}"] + FILE_FLAGS.get(name, [])
+
+
 def build_C(nproc: int = 8, force: bool = False) -> Path:
     hipcc = _hipcc()
     inc, libdir, abi = _torch_flags()
     BUILD.mkdir(parents=True, exist_ok=True)
     headers = list((CSRC / "kernels").glob("*.h"))
-    kern_flags = [f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast-honor-pragmas",
-                  "-munsafe-fp-atomics", f"-I{CSRC}", f"-I{CSRC / 'kernels'}"]
     bind_flags = ["-O2", "-fPIC", "-std=c++17", f"-I{CSRC}", "-D__HIP_PLATFORM_AMD__=1",
                   "-DTORCH_EXTENSION_NAME=_C", "-DTORCH_API_INCLUDE_EXTENSION_H",
                   f"-D_GLIBCXX_USE_CXX11_ABI={abi}"] + inc + _py_includes()
     jobs, objs = [], []
     for src in sorted((CSRC / "kernels").glob("*.hip")):
         obj = BUILD / (src.stem + ".hip.o")
-        flags = kern_flags + FILE_FLAGS.get(src.name, [])
+        flags = kernel_flags(src.name)
         stamp = _digest([src] + headers, " ".join(flags))
         jobs.append((src.name, [hipcc, *flags, "-c", str(src), "-o", str(obj)], obj, stamp))
         objs.append(obj)

@@ -201,33 +201,10 @@ attn_fwd_d64_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out, float*
 // tile kt computes, LDS-DMA as inline asm (invisible to hipcc's waitcnt pass, so it inserts no
 // vmcnt(0) drain of its own), a COUNTED s_waitcnt that leaves the next tile's 4 pieces in flight
 // across the raw s_barrier (the two-buffer kernel above drains every load at every tile: one
-// vmcnt(0) per K/V tile in its ISA).
+// vmcnt(0) per K/V tile in its ISA). desc, dma16 (the form with the literal 0
+// soffset), wait_vm and barrier are lds_ring.h's.
 namespace ring {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// buffer resource over [base, base + bytes): wave-uniform (SGPRs), 32-bit per-lane offsets
-__device__ __forceinline__ u32x4 desc(const void* base, unsigned bytes) {
-  const uint64_t a = (uint64_t)base;
-  return u32x4{(unsigned)a, (unsigned)(a >> 32) & 0xffffu, bytes, 0x00020000u};
-}
-
-// one 1-KB LDS-DMA piece (16 B per lane to lds + 16 lane); M0 = LDS byte address; `s_nop 0`: M0 -> DMA hazard
-__device__ __forceinline__ void dma16(u32x4 d, int voff, const bf16* lds) {
-  const unsigned m0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) bf16*)lds;
-  asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(d), "{m0}"(m0) : "memory");
-}
-
-// s_waitcnt vmcnt(N) lgkmcnt(0)
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 16, "vmcnt field");
-  __builtin_amdgcn_s_waitcnt(0x0070 | N);
-}
-__device__ __forceinline__ void barrier() { asm volatile("s_barrier" ::: "memory"); }
-
 constexpr int SLOT = 2 * A_BK * AD;  // elements: K tile then V tile (16 KB)
-
 }  // namespace ring
 
 template <int WPE>
@@ -819,10 +796,8 @@ attn_bwd_dkdv_d64_ring_kernel(const bf16* __restrict__ qkv, const bf16* __restri
     for (int i = 0; i < 2; ++i)
       dma16(rD, (int)(((int64_t)min(qt * B_BQ + r_[i], T - 1) * otok + c_[i]) * 2), sD_(slot) + (w * 2 + i) * 512);
     // lanes l and l + 16 k read floats qt * 64 + 4 (l & 15) .. + 3 (past T: outside the resource, 0)
-    const unsigned m0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) float*)(sC_(slot) + w * 256);
-    asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"((qt * B_BQ + 4 * (lane & 15)) * 4),
-                 "s"(rC), "{m0}"(m0)
-                 : "memory");
+    const float* const cdst = sC_(slot) + w * 256;
+    dma16(rC, (qt * B_BQ + 4 * (lane & 15)) * 4, cdst);
   };
   // one 64-query tile; MASK: the diagonal tiles and any tile with query rows past T
   auto tile = [&](int qt, auto slot_c, auto mask_c) {

@@ -5,12 +5,9 @@
 #pragma once
 #include <type_traits>
 
-#include "vcx_common.h"
+#include "lds_ring.h"  // sx8 / sx4, and the ring kernels' desc / dma16 / wait_vm / barrier
 
 namespace vcx {
-
-typedef short sx8 __attribute__((ext_vector_type(8)));
-typedef short sx4 __attribute__((ext_vector_type(4)));
 
 constexpr int AD = 64;         // head dim
 constexpr int A_BQ = 128;      // queries per block (4 waves x 32)
@@ -78,7 +75,8 @@ __device__ __forceinline__ f32x16 splat16(float v) {
 // 128-B halves of the 256-B bank row; g is a bijection on 0..7 (16 consecutive rows of one
 // chunk -> 16 distinct 4-bank slots: ds_read_b128 row reads conflict-free) and g(2m), g(2m+1)
 // differ in bit 2 (the 4 rows x 4 chunks of a half-wave ds_read_b64_tr_b16 hit 64 distinct
-// banks). One image serves both the row-operand reads and the transposed reads.
+// banks). One image serves both the row-operand reads and the transposed reads. (128-B rows and 8 chunks: another
+// function than lds_ring.h's swz64 of the GEMMs' 64-B-row image.)
 __device__ __forceinline__ int swz(int r, int chunk) {
   const int k = (r >> 1) & 7;
   return r * 64 + ((chunk ^ (((k & 1) << 2) | (k >> 1))) << 3);
@@ -99,7 +97,8 @@ __device__ __forceinline__ sx8 vt_frag_swz(const bf16* tile, int key0, int dtile
 
 // Bijective XCD-aware block remap (cdna guide §5 T1): hardware block b runs on XCD group b % 8;
 // give each group a CONTIGUOUS range of logical blocks so all query tiles of one (batch, head)
-// share that XCD's L2 copy of K/V.
+// share that XCD's L2 copy of K/V. (Signed / and % and the nwg < 8 guard: different code from lds_ring.h's
+// shift/mask xcd_order, so the attention kernels keep this one.)
 __device__ __forceinline__ int xcd_remap(int b, int nwg) {
   if (nwg < 8) return b;
   const int q = nwg / 8, r = nwg % 8, x = b % 8, i = b / 8;

@@ -30,12 +30,10 @@
 //     same 256-row A panel.
 #include <type_traits>
 
-#include "vcx_common.h"
+#include "lds_ring.h"
 
 namespace vcx {
 namespace gemm {
-
-typedef short sx8 __attribute__((ext_vector_type(8)));
 
 constexpr int BM = 256, BN = 256, BKS = 32, NSLOT = 4, NT = 512;
 constexpr int ROWB = BKS * 2;                  // 64 bytes per row per slot
@@ -45,23 +43,13 @@ constexpr int LDS_BYTES = NSLOT * SLOT_BYTES;  // 128 KB
 
 enum Epi { EPI_STORE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_DGELU = 3, EPI_BIAS_RELU = 4 };
 
-// chunk swizzle F[(row >> 2) & 3] = {0, 2, 3, 1}, packed 2 bits per entry
-__device__ __forceinline__ int swz(int row) { return (0x78 >> (((row >> 2) & 3) * 2)) & 3; }
-
-// s_waitcnt vmcnt(N) lgkmcnt(0) (N < 16; expcnt left at its maximum)
-template <int N>
-__device__ __forceinline__ void waitcnt() {
-  static_assert(N >= 0 && N < 16, "vmcnt field");
-  __builtin_amdgcn_s_waitcnt(0x0070 | N);
-}
-// raw barrier that the compiler may not move LDS reads across (the builtin is IntrNoMem)
-__device__ __forceinline__ void barrier() { asm volatile("s_barrier" ::: "memory"); }
-
+// (this kernel stages with the global_load_lds builtin, which hipcc sees and counts, not with lds_ring.h's asm dma16)
 __device__ __forceinline__ void glds16(const bf16* g, char* lds) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                    (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
 }
 
+// (IEEE divide here, hardware reciprocal in gemm_ps.hip: different results, so the two stay separate)
 __device__ __forceinline__ float gelu_tanh(float x) {
   // 0.5 x (1 + tanh(u)) = x * sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3)
   const float u2 = 1.5957691216057308f * fmaf(0.044715f * x, x * x, x);
@@ -91,25 +79,16 @@ __global__ void __launch_bounds__(NT, 1)
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 2, wn = wid & 3;
 
-  // ---- XCD-aware bijective tile order: consecutive logical tiles share an XCD (and its L2), and
-  // the logical order walks GROUP_M row panels x all column panels in column-major blocks, so the
-  // ~32 tiles an XCD runs at once are a 4 x 8 block (4 A + 8 B panels in flight) instead of one A
-  // panel x 32 B panels (the whole B operand re-streamed by every XCD every round at large N)
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  constexpr int GROUP_M = 4;
-  const int tilesM = nwg / tilesN;
-  const int per_group = GROUP_M * tilesN;
-  const int gfirst = (wg / per_group) * GROUP_M;
-  const int gsize = min(tilesM - gfirst, GROUP_M);
-  const int m0 = (gfirst + (wg % per_group) % gsize) * BM, n0 = ((wg % per_group) / gsize) * BN;
+  // ---- XCD-aware grouped tile order (lds_ring.h)
+  const int nwg = gridDim.x;
+  int tm, tn;
+  grouped_tile(xcd_order(blockIdx.x, nwg), nwg / tilesN, tilesN, tm, tn);
+  const int m0 = tm * BM, n0 = tn * BN;
 
   // ---- LDS-DMA staging: a slice is 32 pieces of 16 rows x 64 B (A: 16, B: 16); wave w moves
   // A pieces w, w+8 and B pieces w, w+8. Lane l of a piece writes LDS bytes [16 l, 16 l + 16):
-  // row l >> 2, physical chunk l & 3, which holds logical chunk (l & 3) ^ swz(row) of that row
-  const int prow = lane >> 2;
-  const int pchunk = (lane & 3) ^ swz(prow);
+  // row l >> 2, physical chunk l & 3, which holds logical chunk (l & 3) ^ swz64(row) of that row
+  const int prow = lane >> 2, pchunk = chunk64(prow, lane & 3);
   // ragged M (the detector's N*H*W rows): rows past M re-read row M - 1 (their outputs are never
   // stored), so no load leaves the operand
   const bf16* a_src = A + (int64_t)min(m0 + wid * 16 + prow, M - 1) * lda + pchunk * 8;
@@ -133,7 +112,7 @@ __global__ void __launch_bounds__(NT, 1)
 
   // ---- fragment reads: lane l -> row (l & 15) of a 16-row block, k chunk (l >> 4)
   const int frow = lane & 15;
-  const int foff = frow * ROWB + (((lane >> 4) ^ swz(frow)) << 4);
+  const int foff = frow * ROWB + (chunk64(frow, lane >> 4) << 4);
   const char* xa = smem + (wm * 128) * ROWB + foff;
   const char* wb = smem + SLOT_A + (wn * 64) * ROWB + foff;
 
@@ -180,7 +159,7 @@ __global__ void __launch_bounds__(NT, 1)
   stage(1);
   stage(2);
   stage(3);
-  waitcnt<12>();
+  wait_vm<12>();
   barrier();
   Frags f0, f1;
   load(f0, 0);
@@ -194,7 +173,7 @@ __global__ void __launch_bounds__(NT, 1)
   // lgkmcnt(0) that covers the prefetch).
   auto step = [&](int s, Frags& fc, Frags& fn, auto STAGE, auto LOAD, auto PEND) {
     constexpr bool st = decltype(STAGE)::value, ld = decltype(LOAD)::value;
-    waitcnt<4 * decltype(PEND)::value>();  // own DMA of slice s + 1 retired; own ds_reads too
+    wait_vm<4 * decltype(PEND)::value>();  // own DMA of slice s + 1 retired; own ds_reads too
     barrier();  // ... everyone's; and nobody still reads the slot of slice s (now s + 4)
     if constexpr (st) stage_piece(s + 4, 0);
     __builtin_amdgcn_sched_barrier(0);

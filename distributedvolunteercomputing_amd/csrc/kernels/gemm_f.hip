@@ -19,7 +19,7 @@
 //     flight across every raw s_barrier, fragments of slice s + 1 read during slice s into a second register set;
 //   * MFMAs as inline asm on pinned accumulators (the builtin let the register allocator rotate them: 68
 //     v_accvgpr_mov per 128 MFMAs in the 4-wave loop);
-//   * 16-B chunks XOR-swizzled per row F[(row >> 2) & 3] = {0, 2, 3, 1} (gemm.hip), applied to the DMA's per-lane
+//   * 16-B chunks XOR-swizzled per row F[(row >> 2) & 3] = {0, 2, 3, 1} (lds_ring.h), applied to the DMA's per-lane
 //     SOURCE address since the DMA writes each wave's 1-KB piece lane-linearly: conflict-free ds_read_b128;
 //   * optional bias added in the epilogue (F.linear's GemmAndBias);
 //   * the output tile leaves through the (then idle) ring as whole row segments, non-temporal stores;
@@ -33,41 +33,14 @@
 // Reference analog: per-frame net.forward, /root/reference/worker.py:248-249 (the pointwise GEMMs).
 #include <type_traits>
 
-#include "vcx_common.h"
+#include "lds_ring.h"
 
 namespace vcx {
 namespace gemm_f {
 
-typedef short sx8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BM = 256, BKS = 32;
 constexpr int ROWB = BKS * 2;           // 64 B per row per slice
 constexpr int SLOT_A = BM * ROWB;       // 16 KB: the A slice
-
-__device__ __forceinline__ int swz(int row) { return (0x78 >> (((row >> 2) & 3) * 2)) & 3; }
-
-// buffer resource words over [base, base + bytes): wave-uniform base and size (SGPRs), 32-bit per-lane offsets
-__device__ __forceinline__ u32x4 desc(const void* base, unsigned bytes) {
-  const uint64_t a = (uint64_t)base;
-  return u32x4{(unsigned)a, (unsigned)(a >> 32) & 0xffffu, bytes, 0x00020000u};
-}
-
-// one 1-KB LDS-DMA piece (16 B per lane to LDS base + 16 lane), M0 = the LDS byte address; `s_nop 0`: the
-// M0 write -> LDS-DMA hazard
-__device__ __forceinline__ void dma16(u32x4 d, int voff, int soff, const char* lds) {
-  const unsigned m0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-  asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(d), "s"(soff), "{m0}"(m0)
-               : "memory");
-}
-
-// s_waitcnt vmcnt(N) lgkmcnt(0) for N up to 63 (vmcnt bits [3:0] and [15:14])
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt field");
-  __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 // Tile 256 x BNT, WM waves along M and WN along N: <2, 2, 256> = 4 waves of 128 x 128 (one wave per SIMD, 256
 // accumulator registers), <2, 4, 256> = 8 waves of 128 x 64 (two waves per SIMD, 128; the default),
@@ -120,27 +93,22 @@ __global__ void __launch_bounds__(G::NT, 1)
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid / WN, wn = wid % WN;
 
-  // ---- XCD-aware bijective tile order (gemm.hip): consecutive logical tiles share an XCD, walked as blocks of
+  // ---- XCD-aware bijective tile order (lds_ring.h): consecutive logical tiles share an XCD, walked as blocks of
   // GROUP_M row panels x all column panels
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wga = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int nwg = gridDim.x, wga = xcd_order(blockIdx.x, nwg);
   // split-K: the grid is splits x tiles, split-major (one XCD's neighbours share the split's K range)
   const int tiles = nwg / splits, split = wga / tiles, wg = wga - split * tiles;
   const int ks0 = split * (K / BKS / splits);  // the split's first K slice
-  constexpr int GROUP_M = 4;
-  const int tilesM = tiles / tilesN;
-  const int per_group = GROUP_M * tilesN;
-  const int gfirst = (wg / per_group) * GROUP_M;
-  const int gsize = min(tilesM - gfirst, GROUP_M);
-  const int m0 = (gfirst + (wg % per_group) % gsize) * BM, n0 = ((wg % per_group) / gsize) * BN;
+  int tm, tn;
+  grouped_tile(wg, tiles / tilesN, tilesN, tm, tn);
+  const int m0 = tm * BM, n0 = tn * BN;
 
   // ---- staging: piece p (0..15) of an operand slice = rows 16 p .. 16 p + 15 (64 lanes x 16 B); wave w moves
   // pieces w + WAVES q (q < HOPS) of A and of B. Lane l: row 16 p + (l >> 2), physical chunk l & 3 holding
   // logical chunk (l & 3) ^ F(row) (F depends on row bits 2..3 only: the same for every piece). Rows past the
   // operand (ragged M, the half column panel of N % 256 == 128) read past the resource: zeros, and their
   // outputs are never stored.
-  const int prow = lane >> 2, pch = (lane & 3) ^ swz(prow);
+  const int prow = lane >> 2, pch = chunk64(prow, lane & 3);
   const int rowsA = min(BM, M - m0), rowsB = min(BN, N - n0);
   const u32x4 ra = CONV ? desc(A, cv.xbytes) : desc(A + (int64_t)m0 * lda, (unsigned)(((int64_t)(rowsA - 1) * lda + K) * 2));
   const u32x4 rb = desc(B + (int64_t)n0 * ldb, (unsigned)(((CONV && cv.btap ? 8 * (int64_t)cv.btap + (1 << cv.lc)
@@ -203,7 +171,7 @@ __global__ void __launch_bounds__(G::NT, 1)
 
   // ---- fragment reads: lane l -> row (l & 15) of a 16-row block, k chunk (l >> 4)
   const int frow = lane & 15;
-  const int foff = frow * ROWB + (((lane >> 4) ^ swz(frow)) << 4);
+  const int foff = frow * ROWB + (chunk64(frow, lane >> 4) << 4);
   auto afrag = [&](int s, int i) {
     return *(const sx8*)(smem + (s % D) * SLOT + (wm * TM + 16 * i) * ROWB + foff);
   };

@@ -22,18 +22,14 @@
 //   * buffer resources per tile (uniform bases in SGPRs, tile-invariant per-lane offsets), and
 //     the bias row resident in LDS (read once per workgroup).
 // Tile walk: tile vb = blockIdx.x + k * gridDim.x through the bijective XCD-aware remap of
-// gemm.hip (grouped 4 x 8 row/column panel blocks per XCD).
+// lds_ring.h (grouped 4 x 8 row/column panel blocks per XCD).
 // Reference analog: the compute hot loop /root/reference/worker.py:249.
 #include <type_traits>
 
-#include "vcx_common.h"
+#include "lds_ring.h"
 
 namespace vcx {
 namespace gemm_ps {
-
-typedef short sx8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 256, BN = 256, BKS = 32, NT = 512;
 constexpr int ROWB = BKS * 2;           // 64 B per row per slot
@@ -54,16 +50,7 @@ constexpr bool has_bias() { return E == EPI_BIAS || E == EPI_BIAS_GELU || E == E
 template <int E>
 constexpr bool reads_c2() { return E == EPI_DGELU || E == EPI_DMUL; }
 
-__device__ __forceinline__ int swz(int row) { return (0x78 >> (((row >> 2) & 3) * 2)) & 3; }
-
-// s_waitcnt vmcnt(N) lgkmcnt(0) (N < 64; expcnt left at its maximum)
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt field");
-  __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void barrier() { asm volatile("s_barrier" ::: "memory"); }
-
+// (hardware reciprocal here, IEEE divide in gemm.hip: different results, so the GELU functions stay separate)
 __device__ __forceinline__ float gelu_tanh_grad(float x) {
   const float x2 = x * x;
   const float u2 = 1.5957691216057308f * fmaf(0.044715f * x, x2, x);
@@ -96,13 +83,6 @@ __device__ __forceinline__ float gelu_tanh(float x) {
 __device__ __forceinline__ void store16(u32x4 v, u32x4 desc, int voff, int soff) {
   asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen nt\n\ts_nop 1" ::"v"(v), "v"(voff), "s"(desc), "s"(soff)
                : "memory");
-}
-
-// raw buffer descriptor words: 48-bit base, stride 0, num_records bytes, the flags word used by
-// __builtin_amdgcn_make_buffer_rsrc elsewhere in the tree
-__device__ __forceinline__ u32x4 desc_of(const void* base, int bytes) {
-  const uint64_t a = (uint64_t)base;
-  return u32x4{(unsigned)a, (unsigned)(a >> 32) & 0xffffu, (unsigned)bytes, 0x00020000u};
 }
 
 // Workgroup geometry: one 512-thread workgroup (8 waves) per CU, 256 x 256 tiles, a 4-slot ring
@@ -139,27 +119,27 @@ __global__ void __launch_bounds__(512, 1)
     __syncthreads();
   }
 
-  // ---- tile coordinates: XCD-aware bijective remap (G is a multiple of 8 or equals tiles)
+  // ---- tile coordinates: the XCD-aware grouped order of lds_ring.h over the virtual block id (G is a multiple
+  // of 8 or equals tiles). The XCD formula is xcd_order(vb, tiles) written out, its tile-invariant q8 / r8 ahead
+  // of the lambda: through the shared helper every instance of this kernel schedules its prologue differently.
   const int q8 = tiles >> 3, r8 = tiles & 7;
-  constexpr int GROUP_M = 4;
   const int tilesM = tiles / tilesN;
   auto coords = [&](int vb, int& m0, int& n0) {
     const int xcd = vb & 7;
     const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (vb >> 3);
-    const int per_group = GROUP_M * tilesN;
-    const int gfirst = (wg / per_group) * GROUP_M;
-    const int gsize = min(tilesM - gfirst, GROUP_M);
-    const int rr = wg - (wg / per_group) * per_group;
-    m0 = (gfirst + rr % gsize) * BM;
-    n0 = (rr / gsize) * BNt;
+    int tm, tn;
+    grouped_tile(wg, tilesM, tilesN, tm, tn);
+    m0 = tm * BM;
+    n0 = tn * BNt;
   };
 
-  // ---- LDS-DMA staging through per-tile buffer resources; per-lane offsets are tile-invariant.
+  // ---- LDS-DMA staging through per-tile buffer resources; per-lane offsets are tile-invariant. (This kernel
+  // stages with the raw_ptr_buffer_load_lds builtin, which hipcc sees and counts, not with lds_ring.h's asm dma16.)
   // A slice is 32 pieces of 16 rows x 64 B (A: 16, B: 16); wave w moves A pieces w, w + 8 and B
   // pieces w, w + 8; lane l writes LDS bytes [16 l, 16 l + 16) of a piece: row l >> 2, physical
-  // chunk l & 3 holding logical chunk (l & 3) ^ swz(row) (swizzle applied to the source address)
+  // chunk l & 3 holding logical chunk (l & 3) ^ swz64(row) (swizzle applied to the source address)
   const int prow = lane >> 2;
-  const int pch = (lane & 3) ^ swz(prow);
+  const int pch = chunk64(prow, lane & 3);
   // piece p < APW: A rows (wid + NW p) * 16 + prow; else B rows (wid + NW (p - APW)) * 16 + prow
   const int a_off0 = ((wid * 16 + prow) * lda + pch * 8) * 2, a_pstep = NW * 16 * lda * 2;
   const int b_off0 = ((wid * 16 + prow) * ldb + pch * 8) * 2, b_pstep = NW * 16 * ldb * 2;
@@ -198,7 +178,7 @@ __global__ void __launch_bounds__(512, 1)
 
   // ---- fragment reads: lane l -> row (l & 15) of a 16-row block, k chunk (l >> 4)
   const int frow = lane & 15;
-  const int foff = frow * ROWB + (((lane >> 4) ^ swz(frow)) << 4);
+  const int foff = frow * ROWB + (chunk64(frow, lane >> 4) << 4);
   const char* xa = smem + (wm * 128) * ROWB + foff;
   const char* wb = smem + SLOTA + (wn * 64) * ROWB + foff;
   // A rows 0..5 are single-buffered (x, refilled right behind the MFMA group that used them);
@@ -258,7 +238,7 @@ __global__ void __launch_bounds__(512, 1)
                   auto VM, auto ST) {
     constexpr bool ld = decltype(LD)::value, st = decltype(ST)::value;
     if (nowait)
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+      wait_lgkm0();
     else
       wait_vm<decltype(VM)::value>();
     barrier();
@@ -316,9 +296,9 @@ __global__ void __launch_bounds__(512, 1)
     else
       asm volatile("s_nop 7\n\ts_nop 4" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    const u32x4 rc = desc_of(C + (int64_t)m0 * ldc + n0, BM * ldc * 2);
+    const u32x4 rc = desc(C + (int64_t)m0 * ldc + n0, BM * ldc * 2);
     u32x4 rc2;
-    if constexpr (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_D) rc2 = desc_of(C2 + (int64_t)m0 * ldc + n0, BM * ldc * 2);
+    if constexpr (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_D) rc2 = desc(C2 + (int64_t)m0 * ldc + n0, BM * ldc * 2);
     float bv[2][8];
     if constexpr (has_bias<EPI>()) {
 #pragma unroll

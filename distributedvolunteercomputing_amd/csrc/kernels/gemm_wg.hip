@@ -12,13 +12,9 @@
 //     raw s_barrier (two slices in flight across every barrier), fragments read TRANSPOSED out of the
 //     token-row LDS image by ds_read_b64_tr_b16 (cdna guide T10); A rows 0..5 single-buffered, rows 6, 7
 //     and the B fragments double-buffered in registers.
-//   * the LDS-DMA is issued by inline asm (dma16), not by the buffer/global_load_lds builtins. With the
-//     builtins, hipcc (ROCm 7.2) cannot tell a pending LDS-DMA from the slot a later
-//     ds_read_b64_tr_b16 reads and drains vmcnt(0) in front of the transposed fragment reads -- 8 full
-//     drains per step in the earlier gemm_tn, whose "waves parked on vmcnt 73 % of the time"
-//     (profiles/r2_gemm_tn.txt) were those drains, not memory latency. Invisible to that pass, the
-//     DMA is ordered only by this kernel's own counted waits: 1165-1229 TF/s at the GPT-2 shapes
-//     against the library's 808-978 (profiles/r5_gemm_wg.txt).
+//   * the LDS-DMA is issued by inline asm (dma16 of lds_ring.h, which says why), not by the
+//     buffer/global_load_lds builtins, and is ordered only by this kernel's own counted waits: 1165-1229
+//     TF/s at the GPT-2 shapes against the library's 808-978 (profiles/r5_gemm_wg.txt).
 //   * measured and dropped (profiles/r5_gemm_wg.txt): wave-role loads (waves 0-3 staging, 4-7 touching
 //     slice t + PF into L2 without ever waiting, the tiles of a split sharing the touches) -- once the
 //     drains were gone the prefetch only cost (pf 4..12: 0-7 % slower than none).
@@ -30,14 +26,10 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "vcx_common.h"
+#include "lds_ring.h"
 
 namespace vcx {
 namespace gemm_wg {
-
-typedef short sx8 __attribute__((ext_vector_type(8)));
-typedef short sx4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 256, BN = 256, BKS = 32, NT = 512;
 constexpr int TROW = 512;                      // bytes per token row of a 256-wide operand slice
@@ -45,8 +37,8 @@ constexpr int TSLOT_A = BKS * TROW;            // 16 KB
 constexpr int SLOT_BYTES = 2 * TSLOT_A;        // 32 KB: A and B slices
 constexpr int LDS_BYTES = 4 * SLOT_BYTES;      // 128 KB ring
 
-// 16-B chunk swizzle of a token row: F(r) = 2 (r & 3 | (r >> 3 & 1) << 2); a half-wave's two transposed
-// reads touch 8 rows (q = r & 3 and the group parity r >> 3 & 1) x 2 chunks, spread over all 16 bank
+// 16-B chunk swizzle of a token row (512-B rows read transposed: another function than lds_ring.h's swz64 of
+// the 64-B-row image): F(r) = 2 (r & 3 | (r >> 3 & 1) << 2); a half-wave's two transposed reads touch 8 rows (q = r & 3 and the group parity r >> 3 & 1) x 2 chunks, spread over all 16 bank
 // slots (conflict-free). LDS-DMA writes lane-linearly, so the swizzle goes on the GLOBAL source address.
 __device__ __forceinline__ int swz(int r) { return ((r & 3) | (((r >> 3) & 1) << 2)) << 1; }
 
@@ -55,34 +47,6 @@ __device__ __forceinline__ sx8 tr_frag(const char* p0, const char* p1) {
   const sx4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) sx4*)(p1));
   return sx8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
-
-// buffer resource words over [base, base + bytes) for inline asm ("s" operand): wave-uniform base and
-// size (SGPRs), 32-bit per-lane offsets
-__device__ __forceinline__ u32x4 desc(const void* base, unsigned bytes) {
-  const uint64_t a = (uint64_t)base;
-  return u32x4{(unsigned)a, (unsigned)(a >> 32) & 0xffffu, (unsigned)bytes, 0x00020000u};
-}
-
-// One 1-KB LDS-DMA piece (16 B per lane to LDS base + 16 lane) as inline asm, M0 = the LDS byte address.
-// Why not __builtin_amdgcn_raw_ptr_buffer_load_lds: hipcc (ROCm 7.2) cannot tell a pending LDS-DMA from
-// the slot a later ds_read_b64_tr_b16 reads, so it drained vmcnt(0) in front of every transposed
-// fragment read of the step -- 8 full drains per step in gemm_tn, the whole pipeline serialised (the
-// "waves parked on vmcnt" of profiles/r2_gemm_tn.txt). Issued as asm, the DMA is invisible to that
-// pass; the kernel's own counted waits (wait_vm) order it. `s_nop 0`: the M0 write -> LDS-DMA hazard.
-__device__ __forceinline__ void dma16(u32x4 d, int voff, int soff, const char* lds) {
-  const unsigned m0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)lds;
-  asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(d), "s"(soff), "{m0}"(m0)
-               : "memory");
-}
-
-// s_waitcnt vmcnt(N) lgkmcnt(0) for N up to 63 (vmcnt bits [3:0] and [15:14])
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt field");
-  __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }  // vmcnt 63: no VM wait
-__device__ __forceinline__ void barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 struct Frags {
   sx8 y[2];  // A fragments of row blocks 6, 7
@@ -118,9 +82,7 @@ __global__ void __launch_bounds__(NT, 1)
 
   // ---- XCD-aware bijective order over (split, tile): consecutive logical ids share an XCD, so the
   // tiles of one split (same token range) run side by side there and share its L2
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = xcd_order(blockIdx.x, gridDim.x);
   const int split = wg / tiles, tile = wg - split * tiles;
   const int tm = tile / tilesN, tn = tile - tm * tilesN;
   const int m0 = tm * BM, n0 = tn * BN;

@@ -123,9 +123,56 @@ void ef_accum(at::Tensor g, at::Tensor e) {
   vcx_ef_accum(g.data_ptr(), e.data_ptr<float>(), g.numel(), cur_stream());
 }
 
+// q8 layout of n elements over P peers: L = P m padded elements, m a multiple of the block, and no
+// more padding than one block per peer; a buffer of records holds L codes + L / 32 bytes of scales
+void check_q8(int64_t n, int64_t L, int64_t P, const at::Tensor& records, const char* what) {
+  const int64_t B = vcx_q8_block();
+  TORCH_CHECK(n > 0 && n < INT32_MAX && P >= 1 && L % (B * P) == 0 && L >= n && L - n < B * P && L < (1ll << 34),
+              what, ": bad layout n=", n, " L=", L, " P=", P);
+  TORCH_CHECK(records.scalar_type() == at::kByte && records.numel() >= L + L / 32, what, ": record buffer too short");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(records.data_ptr()) & 15) == 0, what, ": records must be 16-byte aligned");
+}
+
+// v = e + g encoded into the P records of `wire`; e keeps v - decoded. g: bf16 or fp32 [n], e: fp32 [n]
+void q8_encode(at::Tensor g, at::Tensor e, int64_t L, int64_t P, at::Tensor wire) {
+  CHK(g);
+  CHK(e);
+  CHK(wire);
+  TORCH_CHECK(e.scalar_type() == at::kFloat && g.numel() == e.numel());
+  TORCH_CHECK(g.scalar_type() == at::kBFloat16 || g.scalar_type() == at::kFloat);
+  check_q8(g.numel(), L, P, wire, "q8_encode");
+  vcx_q8_encode(g.data_ptr(), g.scalar_type() == at::kBFloat16, e.data_ptr<float>(), g.numel(), L, (int)P,
+                wire.data_ptr<uint8_t>(), cur_stream());
+}
+
+// recv: P records of a shard of m elements (the peers in rank order); out_record: one record of
+// avg_scale * their sum
+void q8_reduce(at::Tensor recv, int64_t P, int64_t m, double avg_scale, at::Tensor out_record) {
+  CHK(recv);
+  CHK(out_record);
+  check_q8(m, m, 1, out_record, "q8_reduce");
+  TORCH_CHECK(P >= 1 && P <= INT32_MAX && recv.scalar_type() == at::kByte && recv.numel() >= P * (m + m / 32),
+              "q8_reduce: recv must hold P records");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(recv.data_ptr()) & 15) == 0, "q8_reduce: recv must be 16-byte aligned");
+  vcx_q8_reduce(recv.data_ptr<uint8_t>(), (int)P, m, (float)avg_scale, out_record.data_ptr<uint8_t>(), cur_stream());
+}
+
+// records: P records covering L elements; out: bf16 [n], the first n decoded values
+void q8_decode(at::Tensor records, int64_t L, int64_t P, at::Tensor out) {
+  CHK(records);
+  CHK(out);
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16);
+  check_q8(out.numel(), L, P, records, "q8_decode");
+  vcx_q8_decode(records.data_ptr<uint8_t>(), out.numel(), L, (int)P, out.data_ptr(), cur_stream());
+}
+
 }  // namespace
 
 void vcx_register_compress(pybind11::module& m) {
+  m.def("q8_encode", &q8_encode);
+  m.def("q8_reduce", &q8_reduce);
+  m.def("q8_decode", &q8_decode);
+  m.def("q8_block", &vcx_q8_block);
   m.def("topk_ef", &topk_ef);
   m.def("scatter_add", &scatter_add);
   m.def("scatter_add_packed", &scatter_add_packed);

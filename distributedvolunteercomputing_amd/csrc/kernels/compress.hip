@@ -18,6 +18,9 @@
 // HBM-bound (2r FLOP per 4-B element), so they are single-pass streaming kernels with the
 // small Q/P operands served from L2; all matrices of a model are processed by ONE launch per
 // stage through a device-side descriptor table (grouped kernels).
+//
+// q8: 8-bit quantisation in blocks of 128 with one fp32 scale each and error feedback: three
+// streaming kernels (encode, reduce on the shard owner, decode), described at their section below.
 #include "vcx_common.h"
 
 namespace vcx {
@@ -712,6 +715,172 @@ __global__ void __launch_bounds__(256) ef_accum_kernel(const bf16* __restrict__ 
   }
 }
 
+// =====================================================================================
+// q8: 8-bit block quantisation with error feedback
+// =====================================================================================
+// Codec of one block of Q8_BLOCK consecutive fp32 values v: amax = max |v|; blocks with
+// amax < 2^-100 send nothing (scale 0, codes 0); otherwise scale = amax * (1/127),
+// inv = 127 / amax, q = clamp(rint(v * inv), -127, 127), dec = float(q) * scale. Every product and
+// difference is its own fp32 operation (contraction is switched off in these functions), so the
+// kernels agree bit for bit with the torch reference in parallel/compression.py.
+//
+// Wire record of a shard of m elements (m a multiple of Q8_BLOCK): m int8 codes, then m / 128 fp32
+// scales: m + m / 32 bytes, so a record starts on a 4-byte boundary only. A buffer of n elements
+// over P peers is padded to L = P m elements; shard j holds the elements [j m, (j + 1) m).
+//
+// Work split of all three kernels: 8 consecutive elements per lane, 16 lanes per block (4 blocks
+// per wave), the block maximum by 4 cross-lane exchanges inside those 16 lanes.
+// HBM traffic per element: encode 2 (bf16 g) + 4 + 4 (e) + 1.03; reduce (P + 1) * 1.03 of the
+// shard; decode 1.03 + 2.
+constexpr int Q8_BLOCK = 128;
+constexpr int64_t Q8_REC = Q8_BLOCK + 4;  // bytes of one block in a record: codes + its scale
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef u32x2 u32x2_a4 __attribute__((aligned(4)));
+
+__device__ __forceinline__ float q8_group_max(float v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 16));
+  return v;
+}
+
+__device__ __forceinline__ float q8_code(uint32_t w, int j) { return (float)(int8_t)(w >> (8 * j)); }
+
+// this lane's 8 values of a block whose maximum magnitude is amax -> 8 packed codes, the block's
+// scale and the decoded values. Finite input only: with an Inf in the block inv is 0, Inf * 0 is NaN
+// and the clamp turns it into -127 (fmaxf drops a NaN where torch's amax keeps it), so kernel and
+// reference part there and e stays non-finite; non-finite gradients are unsupported
+__device__ __forceinline__ u32x2 q8_quantise8(const float (&v)[8], float amax, float& scale, float (&dec)[8]) {
+#pragma clang fp contract(off)
+  const bool ok = amax >= 0x1p-100f;
+  scale = ok ? amax * (1.0f / 127.0f) : 0.f;
+  const float inv = ok ? 127.0f / amax : 0.f;
+  u32x2 w = {0u, 0u};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float q = fminf(fmaxf(rintf(v[j] * inv), -127.f), 127.f);
+    dec[j] = q * scale;
+    w[j >> 2] |= ((uint32_t)(int)q & 0xffu) << (8 * (j & 3));
+  }
+  return w;
+}
+
+// v = e + g, encode v into the P records of `wire`, e = v - dec. units = L / 8 (a multiple of 16, so
+// the 16 lanes of a block run the same trips and every lane of a wave reaches the exchanges);
+// bps = blocks per shard. Elements in [n, L) encode as zeros and are neither read nor written.
+template <typename GT>
+__global__ void __launch_bounds__(256) q8_encode_kernel(const GT* __restrict__ g, float* __restrict__ e, int64_t n,
+                                                         uint32_t units, uint32_t bps, uint8_t* __restrict__ wire) {
+#pragma clang fp contract(off)
+  const bool vec = ((((uintptr_t)g) | ((uintptr_t)e)) & 15) == 0;
+  for (uint32_t base = blockIdx.x * 256u; base < units; base += gridDim.x * 256u) {
+    const uint32_t u = base + threadIdx.x;
+    const bool live = u < units;
+    const int64_t i = (int64_t)u * 8;
+    const bool full = live && vec && i + 8 <= n;
+    float v[8];
+    if (full) {
+      load8(g, i, v);
+      const f32x4 e0 = *(const f32x4*)(e + i), e1 = *(const f32x4*)(e + i + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[j] = e0[j] + v[j];
+        v[j + 4] = e1[j] + v[j + 4];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = (live && i + j < n) ? e[i + j] + (float)g[i + j] : 0.f;
+    }
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+    amax = q8_group_max(amax);
+    float scale, dec[8];
+    const u32x2 w = q8_quantise8(v, amax, scale, dec);
+    if (!live) continue;
+    const uint32_t blk = u >> 4, sh = blk / bps, rb = blk - sh * bps;
+    uint8_t* r = wire + (int64_t)sh * bps * Q8_REC;
+    *(u32x2_a4*)(r + (int64_t)rb * Q8_BLOCK + (u & 15u) * 8) = w;
+    if ((u & 15u) == 0) *(float*)(r + (int64_t)bps * Q8_BLOCK + (int64_t)rb * 4) = scale;
+    if (full) {
+      f32x4 e0, e1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        e0[j] = v[j] - dec[j];
+        e1[j] = v[j + 4] - dec[j + 4];
+      }
+      *(f32x4*)(e + i) = e0;
+      *(f32x4*)(e + i + 4) = e1;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (i + j < n) e[i + j] = v[j] - dec[j];
+    }
+  }
+}
+
+// recv: the P peers' records of this peer's shard (bps blocks each). acc = sum of the decoded
+// values over p = 0 .. P-1 IN THAT ORDER (fp32), acc *= avg_scale, encode acc into one record.
+__global__ void __launch_bounds__(256) q8_reduce_kernel(const uint8_t* __restrict__ recv, int P, uint32_t bps,
+                                                         float avg_scale, uint8_t* __restrict__ out) {
+#pragma clang fp contract(off)
+  const uint32_t units = bps * 16u;
+  const int64_t rec = (int64_t)bps * Q8_REC, soff = (int64_t)bps * Q8_BLOCK;
+  for (uint32_t base = blockIdx.x * 256u; base < units; base += gridDim.x * 256u) {
+    const uint32_t u = base + threadIdx.x;
+    const bool live = u < units;
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    if (live) {
+      const uint8_t* c = recv + (int64_t)u * 8;
+      const uint8_t* s = recv + soff + (int64_t)(u >> 4) * 4;
+#pragma unroll 4
+      for (int p = 0; p < P; ++p) {
+        const u32x2 w = *(const u32x2_a4*)(c + p * rec);
+        const float sc = *(const float*)(s + p * rec);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = acc[j] + q8_code(w[j >> 2], j & 3) * sc;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = acc[j] * avg_scale;
+    }
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(acc[j]));
+    amax = q8_group_max(amax);
+    float scale, dec[8];
+    const u32x2 w = q8_quantise8(acc, amax, scale, dec);
+    if (!live) continue;
+    *(u32x2_a4*)(out + (int64_t)u * 8) = w;
+    if ((u & 15u) == 0) *(float*)(out + soff + (int64_t)(u >> 4) * 4) = scale;
+  }
+}
+
+// records: the P gathered records (bps blocks each); out[i] = bf16(float(q[i]) * scale) for i < n
+__global__ void __launch_bounds__(256) q8_decode_kernel(const uint8_t* __restrict__ records, int64_t n, uint32_t bps,
+                                                         bf16* __restrict__ out) {
+#pragma clang fp contract(off)
+  const bool vec = (((uintptr_t)out) & 15) == 0;
+  const uint32_t units = (uint32_t)((n + 7) / 8);
+  for (uint32_t u = blockIdx.x * 256u + threadIdx.x; u < units; u += gridDim.x * 256u) {
+    const uint32_t blk = u >> 4, sh = blk / bps, rb = blk - sh * bps;
+    const uint8_t* r = records + (int64_t)sh * bps * Q8_REC;
+    const u32x2 w = *(const u32x2_a4*)(r + (int64_t)rb * Q8_BLOCK + (u & 15u) * 8);
+    const float sc = *(const float*)(r + (int64_t)bps * Q8_BLOCK + (int64_t)rb * 4);
+    const int64_t i = (int64_t)u * 8;
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (bf16)(q8_code(w[j >> 2], j & 3) * sc);
+    if (vec && i + 8 <= n) {
+      *(bf16x8*)(out + i) = o;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (i + j < n) out[i + j] = o[j];
+    }
+  }
+}
+
 }  // namespace vcx
 
 // ====================================================================================== launchers
@@ -817,6 +986,29 @@ void vcx_psgd_reconstruct(const void* desc, int nmat, int nblocks, float* M, con
 void vcx_ef_accum(const void* g, float* e, int64_t n, hipStream_t s) {
   hipLaunchKernelGGL(ef_accum_kernel, dim3(stream_grid(n / 8, 256)), dim3(256), 0, s, (const bf16*)g, e, n / 8);
 }
+
+void vcx_q8_encode(const void* g, int g_is_bf16, float* e, int64_t n, int64_t L, int P, uint8_t* wire, hipStream_t s) {
+  const uint32_t units = (uint32_t)(L / 8), bps = (uint32_t)(L / P / Q8_BLOCK);
+  const int grid = stream_grid(units, 256, 2048);
+  if (g_is_bf16)
+    hipLaunchKernelGGL(q8_encode_kernel<bf16>, dim3(grid), dim3(256), 0, s, (const bf16*)g, e, n, units, bps, wire);
+  else
+    hipLaunchKernelGGL(q8_encode_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)g, e, n, units, bps, wire);
+}
+
+void vcx_q8_reduce(const uint8_t* recv, int P, int64_t m, float avg_scale, uint8_t* out_record, hipStream_t s) {
+  const uint32_t bps = (uint32_t)(m / Q8_BLOCK);
+  hipLaunchKernelGGL(q8_reduce_kernel, dim3(stream_grid(m / 8, 256, 2048)), dim3(256), 0, s, recv, P, bps, avg_scale,
+                     out_record);
+}
+
+void vcx_q8_decode(const uint8_t* records, int64_t n, int64_t L, int P, void* out_bf16, hipStream_t s) {
+  const uint32_t bps = (uint32_t)(L / P / Q8_BLOCK);
+  hipLaunchKernelGGL(q8_decode_kernel, dim3(stream_grid((n + 7) / 8, 256, 2048)), dim3(256), 0, s, records, n, bps,
+                     (bf16*)out_bf16);
+}
+
+int vcx_q8_block() { return Q8_BLOCK; }
 
 int vcx_psgd_desc_size() { return (int)sizeof(MatDesc); }
 int vcx_psgd_rows_per_block() { return 4 * PSGD_ROWS; }

@@ -1,4 +1,4 @@
-// Launchers of kernels/compress.hip (top-k + error feedback, PowerSGD).
+// Launchers of kernels/compress.hip (top-k + error feedback, PowerSGD, q8 block quantisation).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,6 +23,15 @@ int vcx_psgd_orth_rows();
 void vcx_psgd_reconstruct(const void* desc, int nmat, int nblocks, float* M, const float* P, const float* Q,
                           void* out, int rank, int update_m, hipStream_t s);
 void vcx_ef_accum(const void* g, float* e, int64_t n, hipStream_t s);
+// q8 (8-bit codes in blocks of vcx_q8_block() elements, one fp32 scale per block). A record of a
+// shard of m elements is m int8 codes then m / 128 fp32 scales. L = P m >= n, m a multiple of 128.
+// encode: v = e + g, codes and scales of the P shards into `wire` (P records), e = v - decoded
+void vcx_q8_encode(const void* g, int g_is_bf16, float* e, int64_t n, int64_t L, int P, uint8_t* wire, hipStream_t s);
+// recv: P records of one shard; out_record = encode(avg_scale * sum over p = 0..P-1 of decoded record p)
+void vcx_q8_reduce(const uint8_t* recv, int P, int64_t m, float avg_scale, uint8_t* out_record, hipStream_t s);
+// records: P records (L elements); writes the first n decoded values as bf16
+void vcx_q8_decode(const uint8_t* records, int64_t n, int64_t L, int P, void* out_bf16, hipStream_t s);
+int vcx_q8_block();
 int vcx_psgd_desc_size();
 // block tables: psgd_mq / psgd_reconstruct take rows_per_block rows per block; psgd_mtp blocks are
 // (row slab of mtp_rows) x (column chunk of mtp_cols)

@@ -10,7 +10,8 @@ peers may die (--drop-at: fault injection) and join or rejoin (--join) mid-train
 Models: mlp (synthetic MNIST), gpt2[-medium|-large|-xl|-tiny] (random tokens), resnet50 /
 resnet-tiny (synthetic ImageNet), llama3-8b / llama3.2-1b / llama-tiny (random tokens).
 Trainers: localsgd (H local AdamW steps + averaging) | sharded (ZeRO-1 + buddy replicas).
-Compression: none | topk (ratio) | powersgd (rank). Checkpoints: utils/checkpoint.py format.
+Compression: none | topk (ratio) | powersgd (rank) | q8 (8-bit blocks, nothing to tune).
+Checkpoints: utils/checkpoint.py format.
 """
 from __future__ import annotations
 
@@ -91,7 +92,7 @@ def parse(argv=None):
                     help="averaging collective (default: direct for localsgd, rs = reduce-scatter + replica "
                          "shifts for sharded)")
     ap.add_argument("--replicas", type=int, default=2, help="sharded: extra holders of every optimizer shard")
-    ap.add_argument("--compression", default="none", choices=["none", "topk", "powersgd"])
+    ap.add_argument("--compression", default="none", choices=["none", "topk", "powersgd", "q8"])
     ap.add_argument("--topk-ratio", type=float, default=0.01)
     ap.add_argument("--powersgd-rank", type=int, default=4)
     ap.add_argument("--outer-lr", type=float, default=1.0)
@@ -186,6 +187,10 @@ def main(argv=None):
         from ..parallel.compression import PowerSGDCompressor
 
         tr.compressor = PowerSGDCompressor(tr.flat, a.powersgd_rank, device)
+    elif a.compression == "q8":
+        from ..parallel.compression import Quant8Compressor
+
+        tr.compressor = Quant8Compressor(tr.flat.numel, device)
     if a.join and membership is not None:
         tr.join_running_job()
     if a.resume and a.ckpt_dir:

@@ -7,8 +7,12 @@
 * ``PowerSGDCompressor`` — rank-r PowerSGD (Vogels et al., 2019) with warm-started Q and
   error feedback over every matrix of a ``FlatParams`` layout; vectors go uncompressed
   (BASELINE.json config 5: "PowerSGD rank-4 compression").
+* ``Quant8Compressor`` — 8-bit quantisation in blocks of 128 with one fp32 scale each and error
+  feedback (1.03 B per element, any model, nothing to tune), moved like the ``direct``
+  all-reduce: all-to-all of the codes, a fused dequantise-sum-requantise on the shard owner,
+  all-gather of the averaged codes.
 
-Both expose ``allreduce_mean(buf_bf16, group) -> averaged bf16 buffer`` so they plug into
+All expose ``allreduce_mean(buf_bf16, group) -> averaged bf16 buffer`` so they plug into
 ``LocalSGDTrainer`` (compressing the pseudo-gradient) and the sharded data-parallel trainer
 (compressing gradients). GPU tensors use the HIP kernels of ``compress.hip``; CPU tensors
 use the torch reference below (same math).
@@ -117,6 +121,168 @@ class TopKCompressor:
                 self.dense.index_add_(0, w[: self.k].long(), vals / P)
         self.out.copy_(self.dense)
         return self.out
+
+
+_Q8_INV127 = float(np.float32(1.0) / np.float32(127.0))  # the fp32 constant 1.0f / 127.0f
+
+
+def q8_quantise(v: torch.Tensor):
+    """The q8 codec on fp32 blocks ``v [nblocks, 128]`` -> (codes int8 [nblocks, 128], scales fp32
+    [nblocks]). This IS the definition the kernels of compress.hip match bit for bit: every product
+    is one fp32 operation, the divide is correctly rounded, rounding is half to even, and a block
+    whose maximum magnitude is below 2^-100 sends nothing (scale 0, codes 0)."""
+    amax = v.abs().amax(dim=1)
+    ok = amax >= 2.0 ** -100
+    zero = torch.zeros_like(amax)
+    scale = torch.where(ok, amax * _Q8_INV127, zero)
+    # tensor / tensor: one correctly rounded divide (scalar / tensor is reciprocal-then-multiply)
+    inv = torch.where(ok, torch.full_like(amax, 127.0) / amax, zero)
+    q = torch.round(v * inv.unsqueeze(1)).clamp_(-127.0, 127.0)
+    return q.to(torch.int8), scale
+
+
+class Quant8Compressor:
+    """8-bit block quantisation with error feedback: 1.03 B per element instead of bf16's 2, for any
+    model, with nothing to tune. One round over P peers follows the ``direct`` all-reduce:
+    ``encode`` (v = g + e quantised in blocks of 128 into P wire records, e = v - decoded) ->
+    all-to-all of the records -> ``reduce`` on the shard owner (sum of the decoded records in rank
+    order, times 1/P, quantised again into one record) -> all-gather of that record -> ``decode``
+    into a bf16 buffer. The second quantisation has no error feedback: its residual is at most
+    half a code unit of the averaged block and identical on every peer.
+
+    Layout: the n elements are padded to L = ceil(n / (128 P)) 128 P (no padded copy is made: the
+    kernels bounds-check), shard j is the elements [j m, (j + 1) m) with m = L / P, and its record
+    is m int8 codes followed by m / 128 fp32 scales, carried as uint8. ``e`` has length n whatever
+    P is, so a membership change needs no re-layout. Buffers are preallocated for the current P: no
+    per-round allocation in steady state and no host sync on the GPU path. Non-finite gradients are
+    not supported (as with the other compressors): an Inf or NaN stays in ``e`` for good."""
+
+    BLOCK = 128
+
+    def __init__(self, numel: int, device):
+        self.n = int(numel)
+        self.device = torch.device(device)
+        self.e = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+        self._bufs = {}  # (P, name) -> uint8 buffer, see _buf
+        self.out = None  # bf16 [n], allocated on first use
+        self.bytes_sent = 0
+
+    @property
+    def bytes_per_element(self) -> float:
+        """Bytes of a record per element: one code and 1/128 of an fp32 scale."""
+        return 1.0 + 4.0 / self.BLOCK
+
+    def layout(self, P: int):
+        """(L, m, record bytes) for P peers."""
+        step = self.BLOCK * P
+        L = (self.n + step - 1) // step * step
+        m = L // P
+        return L, m, m + m // 32
+
+    def _buf(self, P: int, name: str) -> torch.Tensor:
+        """The preallocated uint8 buffer `name` of the P-peer layout: ``wire`` / ``recv`` /
+        ``gathered`` hold P records, ``record`` one. Allocated on first use (P = 1 needs only
+        ``wire``). Only the current P's buffers are kept: a membership change drops the others
+        (about 3 B per element), and the round after it allocates."""
+        b = self._bufs.get((P, name))
+        if b is None:
+            for stale in [k for k in self._bufs if k[0] != P]:
+                del self._bufs[stale]
+            k = 1 if name == "record" else P
+            b = self._bufs[(P, name)] = torch.zeros(k * self.layout(P)[2], dtype=torch.uint8, device=self.device)
+        return b
+
+    # ------------------------------------------------------------------ the three stages
+    def encode(self, g: torch.Tensor, P: int) -> torch.Tensor:
+        """v = g + e quantised into this peer's P wire records (uint8 [P * record]); e = v - decoded."""
+        L, m, rec = self.layout(P)
+        wire = self._buf(P, "wire")
+        if use_native(g):
+            native().q8_encode(g.contiguous(), self.e, L, P, wire)
+            return wire
+        v = torch.zeros(L, dtype=torch.float32, device=g.device)
+        v[: self.n] = self.e + g.float()
+        q, scale = q8_quantise(v.view(-1, self.BLOCK))
+        dec = q.float() * scale.unsqueeze(1)
+        self.e.copy_((v - dec.view(-1))[: self.n])
+        w = wire.view(P, rec)
+        w[:, :m] = q.view(P, m).view(torch.uint8)
+        w[:, m:] = scale.view(P, m // self.BLOCK).view(torch.uint8)
+        return wire
+
+    @classmethod
+    def _unpack(cls, records: torch.Tensor, P: int):
+        """records uint8 [P * record] -> (codes fp32 [P, m / 128, 128], scales fp32 [P, m / 128, 1])."""
+        w = records.view(P, -1)
+        m = w.shape[1] * 32 // 33
+        q = w[:, :m].contiguous().view(torch.int8).float().view(P, m // cls.BLOCK, cls.BLOCK)
+        scale = w[:, m:].contiguous().view(torch.float32).view(P, m // cls.BLOCK, 1)
+        return q, scale
+
+    def reduce(self, recv: torch.Tensor, P: int) -> torch.Tensor:
+        """recv: the P peers' records of this peer's shard, in rank order -> one record of their mean
+        (fp32 sum in rank order, times 1/P, quantised by the same codec)."""
+        L, m, rec = self.layout(P)
+        record = self._buf(P, "record")
+        avg = float(np.float32(1.0 / P))
+        if use_native(recv):
+            native().q8_reduce(recv, P, m, avg, record)
+            return record
+        q, scale = self._unpack(recv, P)
+        acc = torch.zeros(m // self.BLOCK, self.BLOCK, dtype=torch.float32, device=recv.device)
+        for p in range(P):
+            acc = acc + q[p] * scale[p]
+        acc = acc * avg
+        q2, s2 = q8_quantise(acc)
+        record[:m] = q2.view(-1).view(torch.uint8)
+        record[m:] = s2.view(torch.uint8)
+        return record
+
+    def decode_f32(self, records: torch.Tensor, P: int) -> torch.Tensor:
+        """The decoded fp32 values of the P gathered records, before the bf16 output rounding
+        (torch reference; the tests' view of what a round transmitted)."""
+        q, scale = self._unpack(records, P)
+        return (q * scale).view(-1)[: self.n]
+
+    def decode(self, records: torch.Tensor, P: int) -> torch.Tensor:
+        """records: the P gathered records -> the preallocated bf16 [n] output buffer."""
+        L = self.layout(P)[0]
+        if self.out is None:
+            self.out = torch.empty(self.n, dtype=torch.bfloat16, device=self.device)
+        if use_native(records):
+            native().q8_decode(records, L, P, self.out)
+        else:
+            self.out.copy_(self.decode_f32(records, P))
+        return self.out
+
+    # ------------------------------------------------------------------ state
+    def snapshot(self) -> dict:
+        """Pre-round state for an elastic round that may be aborted and redone."""
+        return {"e": self.e.clone()}
+
+    def restore(self, snap: dict):
+        # fresh tensors: an abandoned (gloo) op of the aborted round may still hold the old ones
+        self.e = snap["e"]
+        self._bufs = {}
+
+    def state_dict(self) -> dict:
+        return {"ef": self.e}
+
+    def load_state_dict(self, d: dict):
+        self.e.copy_(d["ef"].to(self.e.device))
+
+    def allreduce_mean(self, g: torch.Tensor, group) -> torch.Tensor:
+        P = 1 if group is None else group.size
+        wire = self.encode(g, P)
+        if P == 1:
+            return self.decode(wire, 1)
+        recv, record, gathered = self._buf(P, "recv"), self._buf(P, "record"), self._buf(P, "gathered")
+        rec = record.numel()
+        group.alltoall_(recv, wire, [rec] * P, [rec] * P)
+        self.reduce(recv, P)
+        group.all_gather_(gathered, record)
+        self.bytes_sent += 2 * (P - 1) * rec  # (P-1)/P of L + L/32 bytes out in each collective
+        return self.decode(gathered, P)
 
 
 class PowerSGDCompressor:

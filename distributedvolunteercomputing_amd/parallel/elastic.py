@@ -44,7 +44,8 @@ Here every peer
   every survivor's blocking read returns EOF within milliseconds. Inside a guarded collective that
   aborts the generation right away; between rounds it marks the member dead for the next
   arrival. The lease remains the detector for what closes no socket (a hang, SIGSTOP, a
-  partition).
+  partition). A generation's links are opened inside its first guard, right after its
+  communicator is built, so a death in its very first collectives is an EOF too.
 """
 from __future__ import annotations
 
@@ -192,11 +193,23 @@ class _Liveness:
         except Exception:  # noqa: BLE001
             return None
 
-    def watch(self, members):
+    def watch(self, members, wait_s: float = 0.0, give_up=None):
         """Hold a connection to every member (new ones, or a restarted one's new address). Connects
         run on their own threads, so an unreachable address never stalls the caller (the heartbeat
-        thread); only an EOF on an ESTABLISHED connection reports a death."""
+        thread); only an EOF on an ESTABLISHED connection reports a death. With wait_s > 0 the call
+        returns once no connect is outstanding (each link is up, or its attempt failed and is left to
+        the retry), when give_up() turns true, or after wait_s at the latest."""
+        deadline = time.time() + wait_s
+        while self._watch_once(members) and time.time() < deadline and not self._stop.is_set():
+            if give_up is not None and give_up():
+                return
+            time.sleep(0.002)
+
+    def _watch_once(self, members) -> int:
+        """Start the missing connects; returns how many members' links are still outstanding (address
+        not published yet, or connect in flight)."""
         now = time.time()
+        waiting = 0
         for m in members:
             if m == self.pid or self._stop.is_set():
                 continue
@@ -204,13 +217,19 @@ class _Liveness:
             with self._lock:
                 cur = self._conn.get(m)
                 tr = self._trying.get(m)
-                if addr is None or (cur is not None and cur[0] == addr):
+                if addr is None:
+                    waiting += 1
+                    continue
+                if cur is not None and cur[0] == addr:
                     continue
                 if tr is not None and tr[0] == addr and (tr[1] < 0 or now - tr[1] < self.retry_s):
+                    waiting += tr[1] < 0
                     continue  # a connect in flight (time < 0), or it failed a moment ago
                 self._trying[m] = (addr, -1.0)
+                waiting += 1
             threading.Thread(target=self._connect, args=(m, addr), name=f"vcx-live-con-{self.pid}-{m}",
                              daemon=True).start()
+        return waiting
 
     def _connect(self, m, addr):
         host, _, port = addr.rpartition(":")
@@ -334,6 +353,7 @@ class ElasticMembership:
         self.refuse_min = 2
         self.refuse_grace_s = max(2.0, 3.0 * heartbeat_s)
         self.eof_events: list[tuple[int, float]] = []  # (member, time) of every EOF seen
+        self.link_wait_s = 1.0  # a new generation's first guard waits this long at most for its liveness links
         self._ring_pending = False  # an EOF arrived: the heartbeat thread rings the round's bell
         self._tag = ""  # the armed guard's round tag (its verdict key is posted on a trip)
         self._gc: dict[tuple[int, int], list[str]] = {}  # (gen, round) -> keys to delete later
@@ -632,8 +652,19 @@ class ElasticMembership:
             t0 = time.time()
             grp.connect()
             if fresh:  # communicator build of a new generation (RCCL init / gloo full mesh)
-                self.events.append({"event": "connect", "gen": self.gen, "ms": (time.time() - t0) * 1e3,
-                                    "t": time.time(), "bg_build_ms": getattr(grp, "bg_build_ms", None)})
+                ev = {"event": "connect", "gen": self.gen, "ms": (time.time() - t0) * 1e3,
+                      "t": time.time(), "bg_build_ms": getattr(grp, "bg_build_ms", None)}
+                self.events.append(ev)
+                live = self._live
+                if live is not None:
+                    # the links are otherwise opened by the next heartbeat tick: a member killed inside
+                    # the generation's first collectives closed no link yet and cost a whole lease
+                    # (every member published its address before it could build this communicator).
+                    # One TCP connect and hello per member; an abort ends the wait, and the time it
+                    # took is reported on the connect event
+                    t1 = time.time()
+                    live.watch(list(self.members), wait_s=self.link_wait_s, give_up=self._abort.is_set)
+                    ev["links_ms"] = (time.time() - t1) * 1e3
             if getattr(grp, "needs_go", False):
                 self.wait_round_start()
                 grp.needs_go = False

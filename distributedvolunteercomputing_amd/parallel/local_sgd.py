@@ -7,7 +7,7 @@ Per-step GPU work (all on the current HIP stream, graph-capturable):
   zero flat grad -> fwd/bwd -> [grad-norm kernel] -> AdamW prologue -> fused flat AdamW.
 Every H steps (`sync`):
   membership round (elastic only) -> lsgd_delta kernel (bf16 pseudo-gradient)
-  -> [compression: top-k+EF or PowerSGD] -> all-reduce SUM over live peers
+  -> [compression: top-k+EF, PowerSGD or q8+EF] -> all-reduce SUM over live peers
   -> lsgd_apply kernel (average + optional outer Nesterov momentum, writes anchor/master/param).
 
 Reference analog: the chunk (100 frames) is the reference's unit of independent work
@@ -40,7 +40,7 @@ class LocalSGDConfig:
     outer_momentum: float = 0.0
     nesterov: bool = False
     comm_dtype: torch.dtype = torch.bfloat16
-    compression: str = "none"  # none | topk | powersgd
+    compression: str = "none"  # none | topk | powersgd | q8
     topk_ratio: float = 0.01
     powersgd_rank: int = 4
 

@@ -16,7 +16,7 @@ CATS = [  # first match wins
     ("conv dgrad (MIOpen)", r"(?i)bwd_data|BackwardData|conv.*bwd|igemm_bwd|dgrad"),
     ("conv fwd (MIOpen)", r"(?i)conv|igemm_fwd|MIOpen|naive"),
     ("library GEMM (1x1 conv / fc)", r"Cijk|gemm|GEMM"),
-    ("top-k / compression (HIP)", r"topk|hist|radix|select|psgd_"),
+    ("top-k / compression (HIP)", r"topk|hist|radix|select|psgd_|q8_"),
     ("AdamW / local-SGD (HIP)", r"adamw|adam_prologue|grad_sumsq|lsgd"),
     ("split-K / colsum / transpose (HIP)", r"splitk|colsum|transpose|add_f32"),
     ("attention (HIP)", r"attn_"),

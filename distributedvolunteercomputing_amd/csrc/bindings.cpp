@@ -60,6 +60,57 @@ void adamw_flat(at::Tensor param, at::Tensor grad, at::Tensor master, at::Tensor
                  (float)wd, cur_stream());
 }
 
+// compact optimizer state: m_code uint8[n], m_exp uint8[n / 32], v_half fp16[n], v_exp uint8[n / 32]
+void check_compact(at::Tensor m_code, at::Tensor m_exp, at::Tensor v_half, at::Tensor v_exp, int64_t n,
+                   const char* who) {
+  CHECK_IN(m_code, at::kByte);
+  CHECK_IN(m_exp, at::kByte);
+  CHECK_IN(v_half, at::kHalf);
+  CHECK_IN(v_exp, at::kByte);
+  TORCH_CHECK(n % 32 == 0 && m_code.numel() == n && v_half.numel() == n && m_exp.numel() == n / 32 &&
+                  v_exp.numel() == n / 32,
+              who, ": a state of n elements (a multiple of 32) has n codes, n halves and n / 32 bytes of each exponent");
+}
+
+void adamw_flat_compact(at::Tensor param, at::Tensor grad, at::Tensor master, at::Tensor m_code, at::Tensor m_exp,
+                        at::Tensor v_half, at::Tensor v_exp, int64_t n_decay, at::Tensor ostate, double beta1,
+                        double beta2, double eps, double wd) {
+  CHECK_IN(param, kBF);
+  CHECK_IN(grad, kBF);
+  CHECK_IN(master, kF);
+  CHECK_IN(ostate, kF);
+  const int64_t n = param.numel();
+  TORCH_CHECK(grad.numel() == n && master.numel() == n, "adamw_flat_compact: buffers must share a length");
+  check_compact(m_code, m_exp, v_half, v_exp, n, "adamw_flat_compact");
+  TORCH_CHECK(ostate.numel() >= 4);
+  TORCH_CHECK(n_decay >= 0 && n_decay <= n && n_decay % 8 == 0);
+  vcx_adamw_flat_compact(param.data_ptr(), grad.data_ptr(), master.data_ptr<float>(), m_code.data_ptr<uint8_t>(),
+                         m_exp.data_ptr<uint8_t>(), v_half.data_ptr(), v_exp.data_ptr<uint8_t>(), n, n_decay,
+                         ostate.data_ptr<float>(), beta1, beta2, (float)eps, (float)wd, cur_stream());
+}
+
+void optstate_encode(at::Tensor m, at::Tensor v, at::Tensor m_code, at::Tensor m_exp, at::Tensor v_half,
+                     at::Tensor v_exp) {
+  CHECK_IN(m, kF);
+  CHECK_IN(v, kF);
+  const int64_t n = m.numel();
+  TORCH_CHECK(v.numel() == n, "optstate_encode: m and v must share a length");
+  check_compact(m_code, m_exp, v_half, v_exp, n, "optstate_encode");
+  vcx_optstate_encode(m.data_ptr<float>(), v.data_ptr<float>(), m_code.data_ptr<uint8_t>(), m_exp.data_ptr<uint8_t>(),
+                      v_half.data_ptr(), v_exp.data_ptr<uint8_t>(), n, cur_stream());
+}
+
+void optstate_decode(at::Tensor m_code, at::Tensor m_exp, at::Tensor v_half, at::Tensor v_exp, at::Tensor m,
+                     at::Tensor v) {
+  CHECK_IN(m, kF);
+  CHECK_IN(v, kF);
+  const int64_t n = m.numel();
+  TORCH_CHECK(v.numel() == n, "optstate_decode: m and v must share a length");
+  check_compact(m_code, m_exp, v_half, v_exp, n, "optstate_decode");
+  vcx_optstate_decode(m_code.data_ptr<uint8_t>(), m_exp.data_ptr<uint8_t>(), v_half.data_ptr(),
+                      v_exp.data_ptr<uint8_t>(), m.data_ptr<float>(), v.data_ptr<float>(), n, cur_stream());
+}
+
 void lsgd_delta(at::Tensor master, at::Tensor anchor, at::Tensor delta) {
   CHECK_IN(master, kF);
   CHECK_IN(anchor, kF);
@@ -970,6 +1021,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("grad_sumsq", &grad_sumsq);
   m.def("adam_prologue", &adam_prologue);
   m.def("adamw_flat", &adamw_flat);
+  m.def("adamw_flat_compact", &adamw_flat_compact);
+  m.def("optstate_encode", &optstate_encode);
+  m.def("optstate_decode", &optstate_decode);
   m.def("lsgd_delta", &lsgd_delta);
   m.def("lsgd_apply", &lsgd_apply);
   m.def("f32_to_bf16", &f32_to_bf16);

@@ -13,6 +13,9 @@
 // No reference analog ("Fused Adam (HIP)"; BASELINE.json north_star).
 #include "vcx_common.h"
 
+#include <stdexcept>
+#include <string>
+
 namespace vcx {
 
 enum OState { OS_STEP = 0, OS_LR = 1, OS_CLIP = 2, OS_SUMSQ = 3, OS_NUM = 4 };
@@ -214,6 +217,224 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const bf16* __restri
   }
 }
 
+// =====================================================================================
+// compact optimizer state: fp8 m and fp16 v with one power-of-two exponent per block
+// =====================================================================================
+// A block is CS_BLOCK = 32 consecutive elements. Of a range of n elements (n % 32 == 0):
+//   m_code uint8[n]   e4m3fn bit patterns (OCP)     m_exp uint8[n / 32]
+//   v_half fp16[n]                                  v_exp uint8[n / 32]
+// and value = code * 2^(exp byte - 127). Encoding a block: amax = max |x|; amax < 2^-100 gives
+// codes 0 and byte 0. Otherwise amax = f 2^k with f in [0.5, 1) (k = biased exponent - 126) and
+//   m: e = k - 8,  s = clamp(x 2^-e, -240, 240), code = e4m3fn(s) (RNE): the scaled maximum lies in
+//      [128, 256) and 240 is the largest e4m3 value below 256, so decode -> encode is the identity
+//   v: e = k - 15, s = x > 0 ? clamp(x 2^-e, 2^-24, 32752) : 0, code = fp16(s) (RNE): the floor (the
+//      smallest fp16 subnormal) keeps a positive v from decoding to 0 inside a live block, where the
+//      element's update would become m / eps
+// The scale multiplies are exact powers of two (contraction is switched off in the codec
+// functions all the same), so the kernels agree bit for bit with the torch codec in ops/optim.py.
+// 7.06 B/param at rest instead of 12; the fused step moves 18.06 B/param instead of 28.
+// Finite input only: an Inf or NaN moment encodes differently here (fmaxf drops a NaN) and in
+// torch; non-finite gradients are unsupported, as in q8.
+//
+// Work split of all three kernels, as in q8: 8 consecutive elements per lane, 4 lanes per block (16
+// blocks per wave), the block maxima by 2 cross-lane exchanges inside those 4 lanes. units = n / 8 is a
+// multiple of 4, so the 4 lanes of a block run the same trips and every lane reaches the exchanges.
+constexpr int CS_BLOCK = 32;
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float cs_quad_max(float v) {
+  v = fmaxf(v, __shfl_xor(v, 1, 4));
+  v = fmaxf(v, __shfl_xor(v, 2, 4));
+  return v;
+}
+
+__device__ __forceinline__ float cs_amax8(const float (&x)[8]) {
+  float a = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) a = fmaxf(a, fabsf(x[j]));
+  return a;
+}
+
+// 2^(byte - 127); byte 0 (a dead block, all codes 0) decodes with 0
+__device__ __forceinline__ float cs_scale(uint32_t byte) { return __uint_as_float(byte << 23); }
+
+// this lane's 8 values of a block whose maximum magnitude is amax -> 8 e4m3fn codes and the block's byte
+__device__ __forceinline__ u32x2 cs_encode_m8(const float (&x)[8], float amax, uint32_t& byte) {
+#pragma clang fp contract(off)
+  const bool ok = amax >= 0x1p-100f;
+  const uint32_t be = __float_as_uint(amax) >> 23;  // biased exponent: k = be - 126, e = be - 134
+  byte = ok ? be - 7u : 0u;
+  const float inv = __uint_as_float((261u - be) << 23);  // 2^-e
+  u32x2 w = {0u, 0u};
+  if (ok) {
+    float s[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s[j] = fminf(fmaxf(x[j] * inv, -240.f), 240.f);
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      int t = __builtin_amdgcn_cvt_pk_fp8_f32(s[4 * p], s[4 * p + 1], 0, false);
+      w[p] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(s[4 * p + 2], s[4 * p + 3], t, true);
+    }
+  }
+  return w;
+}
+
+__device__ __forceinline__ f16x8 cs_encode_v8(const float (&x)[8], float amax, uint32_t& byte) {
+#pragma clang fp contract(off)
+  const bool ok = amax >= 0x1p-100f;
+  const uint32_t be = __float_as_uint(amax) >> 23;  // k = be - 126, e = be - 141
+  byte = ok ? be - 14u : 0u;
+  const float inv = __uint_as_float((268u - be) << 23);  // 2^-e
+  f16x8 h;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float s = (ok && x[j] > 0.f) ? fminf(fmaxf(x[j] * inv, 0x1p-24f), 32752.f) : 0.f;
+    h[j] = (_Float16)s;
+  }
+  return h;
+}
+
+__device__ __forceinline__ void cs_decode_m8(u32x2 w, uint32_t byte, float (&x)[8]) {
+#pragma clang fp contract(off)
+  const float sc = cs_scale(byte);
+  x[0] = __builtin_amdgcn_cvt_f32_fp8((int)w[0], 0) * sc;
+  x[1] = __builtin_amdgcn_cvt_f32_fp8((int)w[0], 1) * sc;
+  x[2] = __builtin_amdgcn_cvt_f32_fp8((int)w[0], 2) * sc;
+  x[3] = __builtin_amdgcn_cvt_f32_fp8((int)w[0], 3) * sc;
+  x[4] = __builtin_amdgcn_cvt_f32_fp8((int)w[1], 0) * sc;
+  x[5] = __builtin_amdgcn_cvt_f32_fp8((int)w[1], 1) * sc;
+  x[6] = __builtin_amdgcn_cvt_f32_fp8((int)w[1], 2) * sc;
+  x[7] = __builtin_amdgcn_cvt_f32_fp8((int)w[1], 3) * sc;
+}
+
+__device__ __forceinline__ void cs_decode_v8(f16x8 h, uint32_t byte, float (&x)[8]) {
+#pragma clang fp contract(off)
+  const float sc = cs_scale(byte);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = (float)h[j] * sc;
+}
+
+// adamw_flat_kernel with m and v held in the compact format: decode, the arithmetic of
+// adamw_flat_kernel line for line (master and param are updated from the unquantised new m and v
+// of this step), encode. units = n / 8. One difference: the betas arrive in double and 1 - beta is
+// rounded to fp32 once, from the double difference (0.1f at beta1 = 0.9, as the torch reference and
+// torch.optim.AdamW have it), where adamw_flat_kernel subtracts in fp32 (1.f - 0.9f = 0.10000002f).
+// With an unclipped bf16 gradient 0.9 m + 0.1 g lands exactly on code midpoints, and that last-bit
+// difference of the constant alone rounded 3 % of the codes of a step away from the reference's.
+__global__ void __launch_bounds__(256)
+    adamw_flat_compact_kernel(bf16* __restrict__ param, const bf16* __restrict__ grad, float* __restrict__ master,
+                              uint8_t* __restrict__ m_code, uint8_t* __restrict__ m_exp,
+                              _Float16* __restrict__ v_half, uint8_t* __restrict__ v_exp, int64_t units,
+                              int64_t n_decay, const float* __restrict__ ostate, double beta1d, double beta2d,
+                              float eps, float wd) {
+  const float beta1 = (float)beta1d, beta2 = (float)beta2d;
+  const float omb1 = (float)(1.0 - beta1d), omb2 = (float)(1.0 - beta2d);
+  const float step = ostate[OS_STEP];
+  const float lr = ostate[OS_LR];
+  const float clip = ostate[OS_CLIP];
+  const float bc1 = 1.f - powf(beta1, step);
+  const float bc2 = 1.f - powf(beta2, step);
+  const float step_size = lr / bc1;
+  const float inv_sqrt_bc2 = rsqrtf(bc2);
+  for (int64_t first = blockIdx.x * 256ll; first < units; first += (int64_t)gridDim.x * 256) {
+    const int64_t u = first + threadIdx.x;
+    const bool live = u < units;
+    const int64_t base = u * 8, blk = u >> 2;
+    float w[8], mm[8], vv[8];
+    bf16x8 pout;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) mm[j] = vv[j] = 0.f;
+    if (live) {
+      bf16x8 gv = *(const bf16x8*)(grad + base);
+      f32x4 w0 = *(const f32x4*)(master + base), w1 = *(const f32x4*)(master + base + 4);
+      cs_decode_m8(*(const u32x2*)(m_code + base), m_exp[blk], mm);
+      cs_decode_v8(*(const f16x8*)(v_half + base), v_exp[blk], vv);
+      const float decay = (base < n_decay) ? (1.f - lr * wd) : 1.f;
+      w[0] = w0[0]; w[1] = w0[1]; w[2] = w0[2]; w[3] = w0[3];
+      w[4] = w1[0]; w[5] = w1[1]; w[6] = w1[2]; w[7] = w1[3];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float gj = (float)gv[j] * clip;
+        mm[j] = fmaf(beta1, mm[j], omb1 * gj);
+        vv[j] = fmaf(beta2, vv[j], omb2 * gj * gj);
+        float denom = sqrtf(vv[j]) * inv_sqrt_bc2 + eps;
+        w[j] = w[j] * decay - step_size * (mm[j] / denom);
+        pout[j] = (bf16)w[j];
+      }
+    }
+    // every lane of the wave reaches the exchanges (a dead quad carries zeros)
+    const float ma = cs_quad_max(cs_amax8(mm)), va = cs_quad_max(cs_amax8(vv));
+    uint32_t mb, vb;
+    const u32x2 mc = cs_encode_m8(mm, ma, mb);
+    const f16x8 vh = cs_encode_v8(vv, va, vb);
+    if (!live) continue;
+    *(f32x4*)(master + base) = f32x4{w[0], w[1], w[2], w[3]};
+    *(f32x4*)(master + base + 4) = f32x4{w[4], w[5], w[6], w[7]};
+    *(u32x2*)(m_code + base) = mc;
+    *(f16x8*)(v_half + base) = vh;
+    *(bf16x8*)(param + base) = pout;
+    if ((u & 3) == 0) {
+      m_exp[blk] = (uint8_t)mb;
+      v_exp[blk] = (uint8_t)vb;
+    }
+  }
+}
+
+// fp32 m, v -> the four arrays (restore, re-shard). v is taken as non-negative: an element <= 0 encodes as 0.
+__global__ void __launch_bounds__(256)
+    optstate_encode_kernel(const float* __restrict__ m, const float* __restrict__ v, uint8_t* __restrict__ m_code,
+                           uint8_t* __restrict__ m_exp, _Float16* __restrict__ v_half, uint8_t* __restrict__ v_exp,
+                           int64_t units) {
+  for (int64_t first = blockIdx.x * 256ll; first < units; first += (int64_t)gridDim.x * 256) {
+    const int64_t u = first + threadIdx.x;
+    const bool live = u < units;
+    const int64_t base = u * 8, blk = u >> 2;
+    float mm[8], vv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) mm[j] = vv[j] = 0.f;
+    if (live) {
+      const f32x4 m0 = *(const f32x4*)(m + base), m1 = *(const f32x4*)(m + base + 4);
+      const f32x4 v0 = *(const f32x4*)(v + base), v1 = *(const f32x4*)(v + base + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        mm[j] = m0[j];
+        mm[j + 4] = m1[j];
+        vv[j] = v0[j];
+        vv[j + 4] = v1[j];
+      }
+    }
+    const float ma = cs_quad_max(cs_amax8(mm)), va = cs_quad_max(cs_amax8(vv));
+    uint32_t mb, vb;
+    const u32x2 mc = cs_encode_m8(mm, ma, mb);
+    const f16x8 vh = cs_encode_v8(vv, va, vb);
+    if (!live) continue;
+    *(u32x2*)(m_code + base) = mc;
+    *(f16x8*)(v_half + base) = vh;
+    if ((u & 3) == 0) {
+      m_exp[blk] = (uint8_t)mb;
+      v_exp[blk] = (uint8_t)vb;
+    }
+  }
+}
+
+// the four arrays -> fp32 m, v (checkpoint, re-shard)
+__global__ void __launch_bounds__(256)
+    optstate_decode_kernel(const uint8_t* __restrict__ m_code, const uint8_t* __restrict__ m_exp,
+                           const _Float16* __restrict__ v_half, const uint8_t* __restrict__ v_exp,
+                           float* __restrict__ m, float* __restrict__ v, int64_t units) {
+  for (int64_t u = blockIdx.x * 256ll + threadIdx.x; u < units; u += (int64_t)gridDim.x * 256) {
+    const int64_t base = u * 8, blk = u >> 2;
+    float mm[8], vv[8];
+    cs_decode_m8(*(const u32x2*)(m_code + base), m_exp[blk], mm);
+    cs_decode_v8(*(const f16x8*)(v_half + base), v_exp[blk], vv);
+    *(f32x4*)(m + base) = f32x4{mm[0], mm[1], mm[2], mm[3]};
+    *(f32x4*)(m + base + 4) = f32x4{mm[4], mm[5], mm[6], mm[7]};
+    *(f32x4*)(v + base) = f32x4{vv[0], vv[1], vv[2], vv[3]};
+    *(f32x4*)(v + base + 4) = f32x4{vv[4], vv[5], vv[6], vv[7]};
+  }
+}
+
 }  // namespace vcx
 
 // ---------------------------------------------------------------- launchers
@@ -296,4 +517,47 @@ void vcx_splitk_reduce(const void* part, void* acc, int S, int64_t n, int accumu
   const int64_t n8 = n / 8;
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(stream_grid(n8, 256)), dim3(256), 0, s, (const bf16*)part,
                      (bf16*)acc, S, n8, accumulate);
+}
+
+// ---- compact optimizer state. A range the kernels cannot take (n not a multiple of the 32-element
+// block, a pointer off its vector alignment) raises before anything is launched.
+static void cs_check(const char* who, int64_t n, const void* m_code, const void* m_exp, const void* v_half,
+                     const void* v_exp, std::initializer_list<const void*> wide) {
+  if (n < 0 || n % CS_BLOCK != 0)
+    throw std::invalid_argument(std::string(who) + ": n must be a multiple of 32, got " + std::to_string(n));
+  if (!m_code || !m_exp || !v_half || !v_exp) throw std::invalid_argument(std::string(who) + ": null state array");
+  if ((uintptr_t)m_code & 7) throw std::invalid_argument(std::string(who) + ": m_code must be 8-byte aligned");
+  if ((uintptr_t)v_half & 15) throw std::invalid_argument(std::string(who) + ": v_half must be 16-byte aligned");
+  for (const void* p : wide)
+    if (!p || ((uintptr_t)p & 15))
+      throw std::invalid_argument(std::string(who) + ": param, grad, master, m and v must be 16-byte aligned");
+}
+
+void vcx_adamw_flat_compact(void* param, const void* grad, float* master, uint8_t* m_code, uint8_t* m_exp,
+                            void* v_half, uint8_t* v_exp, int64_t n, int64_t n_decay, const float* ostate,
+                            double beta1, double beta2, float eps, float wd, hipStream_t s) {
+  cs_check("adamw_flat_compact", n, m_code, m_exp, v_half, v_exp, {param, grad, master});
+  if (n == 0) return;
+  const int64_t units = n / 8;
+  hipLaunchKernelGGL(adamw_flat_compact_kernel, dim3(stream_grid(units, 256)), dim3(256), 0, s, (bf16*)param,
+                     (const bf16*)grad, master, m_code, m_exp, (_Float16*)v_half, v_exp, units, n_decay, ostate,
+                     beta1, beta2, eps, wd);
+}
+
+void vcx_optstate_encode(const float* m, const float* v, uint8_t* m_code, uint8_t* m_exp, void* v_half,
+                         uint8_t* v_exp, int64_t n, hipStream_t s) {
+  cs_check("optstate_encode", n, m_code, m_exp, v_half, v_exp, {m, v});
+  if (n == 0) return;
+  const int64_t units = n / 8;
+  hipLaunchKernelGGL(optstate_encode_kernel, dim3(stream_grid(units, 256)), dim3(256), 0, s, m, v, m_code, m_exp,
+                     (_Float16*)v_half, v_exp, units);
+}
+
+void vcx_optstate_decode(const uint8_t* m_code, const uint8_t* m_exp, const void* v_half, const uint8_t* v_exp,
+                         float* m, float* v, int64_t n, hipStream_t s) {
+  cs_check("optstate_decode", n, m_code, m_exp, v_half, v_exp, {m, v});
+  if (n == 0) return;
+  const int64_t units = n / 8;
+  hipLaunchKernelGGL(optstate_decode_kernel, dim3(stream_grid(units, 256)), dim3(256), 0, s, m_code, m_exp,
+                     (const _Float16*)v_half, v_exp, m, v, units);
 }

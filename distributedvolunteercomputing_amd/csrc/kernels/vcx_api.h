@@ -9,6 +9,15 @@ void vcx_grad_sumsq(const void* g, int64_t n, float* ostate, hipStream_t s);
 void vcx_adam_prologue(float* ostate, float max_norm, hipStream_t s);
 void vcx_adamw_flat(void* param, const void* grad, float* master, float* m, float* v, int64_t n, int64_t n_decay,
                     const float* ostate, float beta1, float beta2, float eps, float wd, hipStream_t s);
+// compact optimizer state (fp8 m, fp16 v, one exponent byte per 32 elements): n % 32 == 0, m_code 8-byte and
+// every other array 16-byte aligned, or std::invalid_argument
+void vcx_adamw_flat_compact(void* param, const void* grad, float* master, uint8_t* m_code, uint8_t* m_exp,
+                            void* v_half, uint8_t* v_exp, int64_t n, int64_t n_decay, const float* ostate,
+                            double beta1, double beta2, float eps, float wd, hipStream_t s);
+void vcx_optstate_encode(const float* m, const float* v, uint8_t* m_code, uint8_t* m_exp, void* v_half,
+                         uint8_t* v_exp, int64_t n, hipStream_t s);
+void vcx_optstate_decode(const uint8_t* m_code, const uint8_t* m_exp, const void* v_half, const uint8_t* v_exp,
+                         float* m, float* v, int64_t n, hipStream_t s);
 void vcx_lsgd_delta(const float* master, const float* anchor, void* delta, int64_t n, hipStream_t s);
 void vcx_lsgd_apply(const void* avg, float* anchor, float* master, void* param, float* mom, int64_t n,
                     float outer_lr, float mu, int nesterov, float avg_scale, hipStream_t s);

@@ -11,6 +11,7 @@ Models: mlp (synthetic MNIST), gpt2[-medium|-large|-xl|-tiny] (random tokens), r
 resnet-tiny (synthetic ImageNet), llama3-8b / llama3.2-1b / llama-tiny (random tokens).
 Trainers: localsgd (H local AdamW steps + averaging) | sharded (ZeRO-1 + buddy replicas).
 Compression: none | topk (ratio) | powersgd (rank) | q8 (8-bit blocks, nothing to tune).
+Optimizer state: fp32 | compact (fp8 m, fp16 v, one exponent per 32 elements; --opt-state).
 Checkpoints: utils/checkpoint.py format.
 """
 from __future__ import annotations
@@ -95,6 +96,9 @@ def parse(argv=None):
     ap.add_argument("--compression", default="none", choices=["none", "topk", "powersgd", "q8"])
     ap.add_argument("--topk-ratio", type=float, default=0.01)
     ap.add_argument("--powersgd-rank", type=int, default=4)
+    ap.add_argument("--opt-state", default="fp32", choices=["fp32", "compact"],
+                    help="Adam moments at rest: fp32 (12 B/param with the master) or compact (fp8 m, fp16 v with "
+                         "an exponent per 32 elements: 7.06 B/param); checkpoints are fp32 either way")
     ap.add_argument("--outer-lr", type=float, default=1.0)
     ap.add_argument("--outer-momentum", type=float, default=0.0)
     ap.add_argument("--backend", default=None, choices=[None, "nccl", "gloo"])
@@ -171,13 +175,14 @@ def main(argv=None):
         from ..parallel.local_sgd import LocalSGDConfig, LocalSGDTrainer
 
         cfg = LocalSGDConfig(lr=a.lr, H=a.H, algo=a.algo or "direct", outer_lr=a.outer_lr,
-                             outer_momentum=a.outer_momentum,
+                             outer_momentum=a.outer_momentum, opt_state=a.opt_state,
                              comm_dtype=torch.bfloat16 if cuda else torch.float32)
         tr = LocalSGDTrainer(model, cfg, group=group, membership=membership, device=device)
     else:
         from ..parallel.zero import ShardedConfig, ShardedDPTrainer
 
-        tr = ShardedDPTrainer(model, ShardedConfig(lr=a.lr, algo=a.algo or "rs", replicas=a.replicas), group=group,
+        tr = ShardedDPTrainer(model, ShardedConfig(lr=a.lr, algo=a.algo or "rs", replicas=a.replicas,
+                                                   opt_state=a.opt_state), group=group,
                               membership=membership, device=device)
     if a.compression == "topk":
         from ..parallel.compression import TopKCompressor

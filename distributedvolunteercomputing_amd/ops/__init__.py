@@ -8,5 +8,5 @@ from .linear import gemm_nt, linear, mlp_gelu, native_linear_ok, set_gemm_backen
 from .loss import cross_entropy, lm_head_cross_entropy  # noqa: F401
 from .norm import add_layernorm, add_rmsnorm, layernorm, rmsnorm  # noqa: F401
 from .rope import rope_qkv  # noqa: F401
-from .optim import (adamw_step, axpy_bf16, f32_to_bf16, lsgd_apply, lsgd_delta, new_ostate,  # noqa: F401
-                    reduce_bcast_bf16)
+from .optim import (CompactState, adamw_flat_compact, adamw_step, adamw_step_compact, axpy_bf16,  # noqa: F401
+                    check_compact_betas, f32_to_bf16, lsgd_apply, lsgd_delta, new_ostate, reduce_bcast_bf16)

@@ -43,6 +43,9 @@ class LocalSGDConfig:
     compression: str = "none"  # none | topk | powersgd | q8
     topk_ratio: float = 0.01
     powersgd_rank: int = 4
+    # fp32: m and v in fp32 (12 B/param with the master) | compact: fp8 m and fp16 v with one exponent
+    # per 32 elements (7.06 B/param; ops/optim.py CompactState); checkpoints hold fp32 either way
+    opt_state: str = "fp32"
 
 
 @dataclass
@@ -65,8 +68,16 @@ class LocalSGDTrainer:
         self.buffers = FlatBuffers(model)  # BN running stats: averaged at every sync
         n = self.flat.numel
         self.master = self.flat.param.float()
-        self.m = torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.v = torch.zeros(n, dtype=torch.float32, device=self.device)
+        if cfg.opt_state not in ("fp32", "compact"):
+            raise ValueError(f"opt_state must be 'fp32' or 'compact', got {cfg.opt_state!r}")
+        self.cstate = None  # compact mode: the moments live here and self.m / self.v are None
+        if cfg.opt_state == "compact":
+            ops.check_compact_betas(cfg.betas)
+            self.m = self.v = None
+            self.cstate = ops.CompactState.zeros(n, self.device)
+        else:
+            self.m = torch.zeros(n, dtype=torch.float32, device=self.device)
+            self.v = torch.zeros(n, dtype=torch.float32, device=self.device)
         self.anchor = self.master.clone()
         self.delta = torch.zeros(n, dtype=cfg.comm_dtype, device=self.device)
         self.outer_mom = torch.zeros(n, dtype=torch.float32, device=self.device) if cfg.outer_momentum > 0 else None
@@ -99,9 +110,12 @@ class LocalSGDTrainer:
 
     def optimizer_step(self):
         c = self.cfg
-        ops.adamw_step(self.flat.param, self.flat.grad, self.master, self.m, self.v, self.ostate,
-                       n_decay=self.flat.n_decay, beta1=c.betas[0], beta2=c.betas[1], eps=c.eps,
-                       wd=c.weight_decay, max_norm=c.max_grad_norm)
+        kw = dict(n_decay=self.flat.n_decay, beta1=c.betas[0], beta2=c.betas[1], eps=c.eps, wd=c.weight_decay,
+                  max_norm=c.max_grad_norm)
+        if self.cstate is not None:
+            ops.adamw_step_compact(self.flat.param, self.flat.grad, self.master, self.cstate, self.ostate, **kw)
+        else:
+            ops.adamw_step(self.flat.param, self.flat.grad, self.master, self.m, self.v, self.ostate, **kw)
 
     # ------------------------------------------------------------------ hipGraph capture
     def capture(self, x, y, warmup: int = 3):
@@ -374,7 +388,11 @@ class LocalSGDTrainer:
 
     # ------------------------------------------------------------------ state
     def state_tensors(self):
-        return {"master": self.master, "m": self.m, "v": self.v, "anchor": self.anchor, "ostate": self.ostate}
+        if self.cstate is not None:
+            moments = dict(zip(self.cstate.FIELDS, self.cstate.arrays()))
+        else:
+            moments = {"m": self.m, "v": self.v}
+        return {"master": self.master, **moments, "anchor": self.anchor, "ostate": self.ostate}
 
     def checkpoint_slice(self):
         """This peer's 1/P share of the (synchronised) state: call right after a sync round,
@@ -386,8 +404,10 @@ class LocalSGDTrainer:
         P = 1 if self.group is None else self.group.size
         r = 0 if self.group is None else self.group.rank
         lo, hi = self.flat.shard_bounds(r, P)
-        t = {"master": self.anchor[lo:hi], "m": mean_slice(self.group, self.m, lo, hi),
-             "v": mean_slice(self.group, self.v, lo, hi)}
+        # compact: the checkpoint holds fp32 moments either way, decoded before the mean over the peers
+        m, v = self.cstate.to_fp32() if self.cstate is not None else (self.m, self.v)
+        t = {"master": self.anchor[lo:hi], "m": mean_slice(self.group, m, lo, hi),
+             "v": mean_slice(self.group, v, lo, hi)}
         if self.outer_mom is not None:
             t["outer_mom"] = self.outer_mom[lo:hi]  # identical on every peer (updated from the average)
         if self.compressor is not None:
@@ -409,8 +429,12 @@ class LocalSGDTrainer:
         dev = self.device
         self.master.copy_(reader.read_range("master", 0, n).to(dev))
         self.anchor.copy_(self.master)
-        self.m.copy_(reader.read_range("m", 0, n).to(dev))
-        self.v.copy_(reader.read_range("v", 0, n).to(dev))
+        m, v = reader.read_range("m", 0, n).to(dev), reader.read_range("v", 0, n).to(dev)
+        if self.cstate is not None:
+            self.cstate.load_fp32(m, v)
+        else:
+            self.m.copy_(m)
+            self.v.copy_(v)
         if self.outer_mom is not None:
             self.outer_mom.copy_(reader.read_range("outer_mom", 0, n).to(dev))
         _, ost = reader.params()

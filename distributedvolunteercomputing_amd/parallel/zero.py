@@ -56,6 +56,10 @@ class ShardedConfig:
     replicate: bool = True  # False: no replicas (replicas = 0)
     algo: str = "rs"  # rs (reduce-scatter + replica shifts) | rccl | rs_ag | butterfly | ring | direct
     allow_state_loss: bool = False  # restart a lost shard from the bf16 params instead of raising
+    # fp32: m and v in fp32 (12 B/param with the master) | compact: fp8 m and fp16 v with one exponent
+    # per 32 elements (7.06 B/param; ops/optim.py CompactState). Re-shard pieces and checkpoints are fp32
+    # either way; every held shard (primary or replica) keeps "cs" in place of "m" and "v"
+    opt_state: str = "fp32"
 
 
 class ShardedDPTrainer:
@@ -63,6 +67,11 @@ class ShardedDPTrainer:
         self.model = model
         self.cfg = cfg
         self.device = torch.device(device or next(model.parameters()).device)
+        if cfg.opt_state not in ("fp32", "compact"):
+            raise ValueError(f"opt_state must be 'fp32' or 'compact', got {cfg.opt_state!r}")
+        self.compact = cfg.opt_state == "compact"
+        if self.compact:
+            ops.check_compact_betas(cfg.betas)
         self.flat = FlatParams(model, device=self.device)
         self.buffers = FlatBuffers(model)
         self.membership = membership
@@ -102,15 +111,29 @@ class ShardedDPTrainer:
                 return torch.zeros(b - a, dtype=torch.float32, device=self.device)
             return full[a:b].to(torch.float32, copy=True)
 
+        def moments(a, b):
+            if not self.compact:
+                return {"m": cut(full_m, a, b), "v": cut(full_v, a, b)}
+            if full_m is None and full_v is None:
+                return {"cs": ops.CompactState.zeros(b - a, self.device)}
+            return {"cs": ops.CompactState.from_fp32(cut(full_m, a, b), cut(full_v, a, b))}
+
         self.master = cut(full_master, lo, hi)
-        self.m = cut(full_m, lo, hi)
-        self.v = cut(full_v, lo, hi)
+        self._set_moments(moments(lo, hi))
         self.reps = []  # replicas: shards (r-1) .. (r-R) of the current layout
         for i in range(1, self.n_replicas + 1):
             j = (r - i) % P
             a, b = self.flat.shard_bounds(j, P)
-            self.reps.append({"shard": j, "range": (a, b), "master": cut(full_master, a, b),
-                              "m": cut(full_m, a, b), "v": cut(full_v, a, b)})
+            self.reps.append({"shard": j, "range": (a, b), "master": cut(full_master, a, b), **moments(a, b)})
+
+    def _set_moments(self, d):
+        """The primary's moments: fp32 `m`, `v`, or the compact `cs` (then m and v are None)."""
+        self.m, self.v, self.cs = d.get("m"), d.get("v"), d.get("cs")
+
+    def _held(self):
+        """Every shard this peer holds, the primary first, as dicts like the entries of `reps`."""
+        mom = {"cs": self.cs} if self.compact else {"m": self.m, "v": self.v}
+        return [{"shard": self.rank, "range": self.prim, "master": self.master, **mom}] + self.reps
 
     @property
     def back(self):  # first replica's range (compat)
@@ -118,7 +141,8 @@ class ShardedDPTrainer:
 
     def checkpoint_slice(self):
         lo, hi = self.prim
-        t = {"master": self.master, "m": self.m, "v": self.v}
+        m, v = self.cs.to_fp32() if self.compact else (self.m, self.v)  # the file holds fp32 either way
+        t = {"master": self.master, "m": m, "v": v}
         if self.compressor is not None:
             t["ef"] = mean_slice(self.group, self.compressor.state_dict()["ef"], lo, hi)
         return lo, hi, t
@@ -138,20 +162,24 @@ class ShardedDPTrainer:
         param, ost = reader.params()
         self.flat.param.copy_(param.to(dev))
         self.ostate.copy_(ost.to(dev))
-        lo, hi = self.prim
-        self.master.copy_(reader.read_range("master", lo, hi).to(dev))
-        self.m.copy_(reader.read_range("m", lo, hi).to(dev))
-        self.v.copy_(reader.read_range("v", lo, hi).to(dev))
-        for rep in self.reps:
-            a, b = rep["range"]
-            for k in ("master", "m", "v"):
-                rep[k].copy_(reader.read_range(k, a, b).to(dev))
+        for h in self._held():
+            a, b = h["range"]
+            h["master"].copy_(reader.read_range("master", a, b).to(dev))
+            m, v = reader.read_range("m", a, b).to(dev), reader.read_range("v", a, b).to(dev)
+            if self.compact:
+                h["cs"].load_fp32(m, v)
+            else:
+                h["m"].copy_(m)
+                h["v"].copy_(v)
         restore_extras(self, reader)
         self.t = reader.step
 
     def state_bytes(self) -> int:
-        n = self.master.numel() + sum(rep["master"].numel() for rep in self.reps)
-        return 12 * n
+        """Bytes of optimizer state (master and moments) of every shard this peer holds."""
+        n = 0
+        for h in self._held():
+            n += 4 * h["master"].numel() + (h["cs"].nbytes if self.compact else 8 * h["master"].numel())
+        return n
 
     # ------------------------------------------------------------------ step
     def step(self, x, y):
@@ -234,13 +262,17 @@ class ShardedDPTrainer:
         allreduce_sum_(avg, self.group, "rccl" if algo == "rs" else algo)
         return avg.div_(P)
 
-    def _adam_range(self, avg, a, b, master, m, v):
+    def _adam_range(self, avg, a, b, master, m, v, cs=None):
         c = self.cfg
         n_decay = max(0, min(self.flat.n_decay - a, b - a))
         n_decay -= n_decay % 8
         # the flat kernels read ostate (step/lr/clip) — shared by all ranges, prologue once
         C = ops.native() if self.flat.param.is_cuda else None
-        if C is not None:
+        if cs is not None:
+            # primary and replicas run the same kernel on the same bytes, so they stay bit-identical
+            ops.adamw_flat_compact(self.flat.param[a:b], avg[a:b], master, cs, self.ostate, n_decay=n_decay,
+                                   beta1=c.betas[0], beta2=c.betas[1], eps=c.eps, wd=c.weight_decay)
+        elif C is not None:
             C.adamw_flat(self.flat.param[a:b], avg[a:b], master, m, v, n_decay, self.ostate, c.betas[0], c.betas[1],
                          c.eps, c.weight_decay)
         else:
@@ -278,11 +310,9 @@ class ShardedDPTrainer:
             if coef != 1.0:
                 avg = (avg.float() * coef).to(avg.dtype)
                 self.ostate[2] = 1.0
-        lo, hi = self.prim
-        self._adam_range(avg, lo, hi, self.master, self.m, self.v)
-        for rep in self.reps:
-            a, b = rep["range"]
-            self._adam_range(avg, a, b, rep["master"], rep["m"], rep["v"])
+        for h in self._held():
+            a, b = h["range"]
+            self._adam_range(avg, a, b, h["master"], h.get("m"), h.get("v"), h.get("cs"))
 
     def _gather_params(self, elastic: bool):
         """All-gather of the updated bf16 primaries. Elastic: into a fresh buffer that the caller
@@ -408,9 +438,14 @@ class ShardedDPTrainer:
                         **{f: torch.zeros(b - a, dtype=torch.float32, device=dev) for f in ("master", "m", "v")}})
 
         def old_piece(j, x, y):
+            # fp32 (master, m, v) of [x, y). Compact: decoded piece by piece (nothing at full-shard size);
+            # pieces start and end on multiples of ALIGN = 64 elements, so whole 32-element blocks
+            # travel and the destination's encode gives back the very same bytes
             st = self._shard_state_old(j, my_old, old_P)
             aj = self.flat.shard_bounds(j, old_P)[0]
-            return [t[x - aj : y - aj] for t in st]
+            if self.compact:
+                return [st["master"][x - aj : y - aj], *st["cs"].to_fp32(x - aj, y - aj)]
+            return [st[f][x - aj : y - aj] for f in ("master", "m", "v")]
 
         send = [[] for _ in range(new_P)]
         recv = [[] for _ in range(new_P)]
@@ -460,19 +495,22 @@ class ShardedDPTrainer:
             ops.f32_to_bf16(dst[0]["master"], mine) if mine.is_cuda else mine.copy_(dst[0]["master"])
             params = torch.empty_like(self.flat.param)
             new_group.all_gather_(params, mine)
+        if self.compact:  # the assembled fp32 moments of every destination shard go back to the compact format
+            for h in dst:
+                h["cs"] = ops.CompactState.from_fp32(h.pop("m"), h.pop("v"))
         ev = {"t": self.t, "old": L, "new": members, "lost": [(x, y) for *_, x, y in lost],
               "bytes_sent": moved, "bytes_changed": changed, "ms": (time.perf_counter() - t0) * 1e3}
         return dst, ost, bufs, params, lost, ev
 
     def _shard_state_old(self, j, my_old, old_P):
-        """(master, m, v) this peer held for shard j of the OLD layout (index my_old of old_P)."""
+        """What this peer held for shard j of the OLD layout (index my_old of old_P): a dict as in `_held`."""
         if my_old is None:
             raise StateLost(f"asked for shard {j} but this peer held no shard")
         if j == my_old:
-            return self.master, self.m, self.v
+            return self._held()[0]
         for rep in self.reps:
             if rep["shard"] == j:
-                return rep["master"], rep["m"], rep["v"]
+                return rep
         raise StateLost(f"shard {j} expected on this peer (old index {my_old} of {old_P})")
 
     def _reshard_apply(self, new_group, dst, ost, bufs, params, lost, ev):
@@ -488,9 +526,9 @@ class ShardedDPTrainer:
         self.group = new_group
         self._layout_members = members
         self.prim = dst[0]["range"]
-        self.master, self.m, self.v = dst[0]["master"], dst[0]["m"], dst[0]["v"]
-        self.reps = [{"shard": r["shard"], "range": r["range"], "master": r["master"], "m": r["m"], "v": r["v"]}
-                     for r in dst[1:]]
+        self.master = dst[0]["master"]
+        self._set_moments(dst[0])
+        self.reps = [dict(r) for r in dst[1:]]
         if params is not None:
             self.flat.param.copy_(params)
         else:  # a single survivor holds everything: its parameters from its masters

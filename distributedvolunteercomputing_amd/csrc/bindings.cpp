@@ -601,6 +601,37 @@ void reduce_bcast_bf16(at::Tensor in, c10::optional<at::Tensor> out, c10::option
                         cur_stream());
 }
 
+// Robust middle step of the direct all-reduce (robust.hip). Everything is checked here, before the launcher's
+// own checks, so a refused call leaves out, mine and counts unwritten.
+void trimmed_reduce_bcast_bf16(at::Tensor in, c10::optional<at::Tensor> out, c10::optional<at::Tensor> mine, int64_t P,
+                               int64_t trim, int64_t live_mask, double inv, c10::optional<at::Tensor> counts) {
+  TORCH_CHECK(in.is_cuda() && in.scalar_type() == at::kBFloat16 && in.is_contiguous(),
+              "trimmed_reduce_bcast: in must be a contiguous bf16 GPU tensor");
+  TORCH_CHECK(P >= 1 && P <= 16, "trimmed_reduce_bcast: P must be in 1..16, got ", P);
+  TORCH_CHECK(live_mask > 0 && (live_mask >> P) == 0,
+              "trimmed_reduce_bcast: live_mask must name at least one of the P rows and no other, got ", live_mask);
+  TORCH_CHECK(trim >= 0, "trimmed_reduce_bcast: trim must be >= 0");
+  const int64_t n = in.numel() / P;
+  TORCH_CHECK(n * P == in.numel() && n % 8 == 0, "trimmed_reduce_bcast: numel must be P * n with n % 8 == 0");
+  auto aligned = [](const at::Tensor& t, uintptr_t a) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % a == 0; };
+  TORCH_CHECK(aligned(in, 16), "trimmed_reduce_bcast: in must be 16-byte aligned");
+  if (out)
+    TORCH_CHECK(out->is_cuda() && out->get_device() == in.get_device() && out->numel() == in.numel() &&
+                    out->is_contiguous() && out->scalar_type() == at::kBFloat16 && aligned(*out, 16),
+                "trimmed_reduce_bcast: out must match in (bf16, same length, 16-byte aligned)");
+  if (mine)
+    TORCH_CHECK(mine->is_cuda() && mine->get_device() == in.get_device() && mine->numel() == n &&
+                    mine->is_contiguous() && mine->scalar_type() == at::kBFloat16 && aligned(*mine, 16),
+                "trimmed_reduce_bcast: mine must hold n bf16, 16-byte aligned");
+  if (counts)
+    TORCH_CHECK(counts->is_cuda() && counts->get_device() == in.get_device() && counts->numel() == P &&
+                    counts->is_contiguous() && counts->scalar_type() == at::kLong,
+                "trimmed_reduce_bcast: counts must hold P int64 on in's device");
+  vcx_trimmed_reduce_bcast_bf16(in.data_ptr(), opt_ptr(out), opt_ptr(mine), (int)P, n, (int)std::min<int64_t>(trim, 16),
+                                (uint32_t)live_mask, (float)inv, counts ? counts->data_ptr<int64_t>() : nullptr,
+                                cur_stream());
+}
+
 void axpy_bf16(at::Tensor src, at::Tensor acc, double scale) {
   CHECK_IN(src, kBF);
   CHECK_IN(acc, kBF);
@@ -1029,6 +1060,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("f32_to_bf16", &f32_to_bf16);
   m.def("axpy_bf16", &axpy_bf16);
   m.def("reduce_bcast_bf16", &reduce_bcast_bf16);
+  m.def("trimmed_reduce_bcast_bf16", &trimmed_reduce_bcast_bf16);
   m.def("gemm_nt_supported", &gemm_nt_supported);
   m.def("gemm_nt_supported_epi", &gemm_nt_supported_epi);
   m.def("gemm_ps_supported", &gemm_ps_supported);

@@ -57,6 +57,13 @@ void vcx_add_f32_into_bf16(float* in, void* out, int n, int accumulate, int zero
 void vcx_reduce_bcast_bf16(const void* in, void* out, void* mine, int P, int64_t n, hipStream_t s);
 void vcx_splitk_reduce(const void* part, void* acc, int S, int64_t n, int accumulate, hipStream_t s);
 
+// robust.hip: coordinate-wise trimmed mean of the live rows of in [P, n] (bf16), written to every row of
+// out [P, n] (may alias in, or null) and to mine [n] (or null); counts[k] (int64[P] or null) += the elements
+// of live row k that were trimmed. P <= 16, n % 8 == 0, inv = fp32 1 / (K - 2f); throws std::invalid_argument
+// on anything else before a launch
+void vcx_trimmed_reduce_bcast_bf16(const void* in, void* out, void* mine, int P, int64_t n, int trim,
+                                   uint32_t live_mask, float inv, int64_t* counts, hipStream_t s);
+
 // norm_act.hip
 void vcx_ln_fwd(const void* a, const void* b, void* xout, void* y, const void* w, const void* bias, float* mean,
                 float* rstd, int R, int C, float eps, int rms, const void* bb, hipStream_t s);

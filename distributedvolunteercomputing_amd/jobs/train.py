@@ -11,6 +11,8 @@ Models: mlp (synthetic MNIST), gpt2[-medium|-large|-xl|-tiny] (random tokens), r
 resnet-tiny (synthetic ImageNet), llama3-8b / llama3.2-1b / llama-tiny (random tokens).
 Trainers: localsgd (H local AdamW steps + averaging) | sharded (ZeRO-1 + buddy replicas).
 Compression: none | topk (ratio) | powersgd (rank) | q8 (8-bit blocks, nothing to tune).
+Aggregation (localsgd): mean | trimmed (--trim) | median: the coordinate-wise trimmed mean survives peers
+that stay alive and send wrong numbers (--byzantine: fault injection for exactly that).
 Optimizer state: fp32 | compact (fp8 m, fp16 v, one exponent per 32 elements; --opt-state).
 Checkpoints: utils/checkpoint.py format.
 """
@@ -80,6 +82,14 @@ class SyntheticData:
         return x, self.y[sl]
 
 
+def _fill_nan(d):
+    d.fill_(float("nan"))
+
+
+# --byzantine: what the peer does to its pseudo-gradient before every averaging round
+BYZANTINE = {"none": None, "nan": _fill_nan, "flip": lambda d: d.mul_(-1.0), "scale": lambda d: d.mul_(1e4)}
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(prog="train", description=__doc__.splitlines()[0])
     ap.add_argument("--model", default="gpt2")
@@ -114,6 +124,13 @@ def parse(argv=None):
                     help="admission token for a coordinator started with one (tjoin)")
     ap.add_argument("--join", action="store_true", help="join a running job instead of bootstrapping")
     ap.add_argument("--drop-at", type=int, default=-1, help="fault injection: crash this peer at that step")
+    ap.add_argument("--byzantine", default="none", choices=list(BYZANTINE),
+                    help="fault injection: this peer stays alive and sends a wrong pseudo-gradient to every "
+                         "averaging round (nan: all NaN, flip: times -1, scale: times 1e4)")
+    ap.add_argument("--aggregate", default="mean", choices=["mean", "trimmed", "median"],
+                    help="localsgd: how the peers' pseudo-gradients become one. trimmed / median: coordinate-wise "
+                         "trimmed mean, survives up to --trim wrong peers per coordinate")
+    ap.add_argument("--trim", type=int, default=1, help="--aggregate trimmed: values dropped at each end")
     ap.add_argument("--ckpt-dir", default=None)
     ap.add_argument("--ckpt-every", type=int, default=0)
     ap.add_argument("--resume", action="store_true")
@@ -121,7 +138,14 @@ def parse(argv=None):
     ap.add_argument("--metrics", default=None, help="JSONL metrics file")
     ap.add_argument("--trace-dir", default=config.get().trace_dir or None,
                     help="write per-stage device-time spans (HIP events) as JSONL here")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.trainer == "sharded" and a.aggregate != "mean":
+        ap.error(f"--aggregate {a.aggregate} needs --trainer localsgd (the sharded trainer's reduce-scatter is a sum)")
+    if a.trainer == "sharded" and a.byzantine != "none":
+        ap.error("--byzantine needs --trainer localsgd")
+    if a.trim < 0:
+        ap.error("--trim must be >= 0")
+    return a
 
 
 def main(argv=None):
@@ -176,8 +200,10 @@ def main(argv=None):
 
         cfg = LocalSGDConfig(lr=a.lr, H=a.H, algo=a.algo or "direct", outer_lr=a.outer_lr,
                              outer_momentum=a.outer_momentum, opt_state=a.opt_state,
-                             comm_dtype=torch.bfloat16 if cuda else torch.float32)
+                             comm_dtype=torch.bfloat16 if cuda else torch.float32,
+                             aggregate=a.aggregate, trim=a.trim)
         tr = LocalSGDTrainer(model, cfg, group=group, membership=membership, device=device)
+        tr.delta_hook = BYZANTINE[a.byzantine]
     else:
         from ..parallel.zero import ShardedConfig, ShardedDPTrainer
 
@@ -253,6 +279,8 @@ def main(argv=None):
             rec = {"peer": rank, "step": step, "loss": float(loss), "ms_per_step": (now - t_last) * 1e3 / a.log_every,
                    "members": (tr.group.size if tr.group is not None else 1),
                    "gen": membership.gen if membership else 0}
+            if getattr(out, "synced", False) and getattr(tr, "trim_share", None) is not None:
+                rec["trim_share"] = [round(s, 4) for s in tr.trim_share]  # per rank, of the round just done
             t_last = now
             print(json.dumps(rec), flush=True)
             if log:

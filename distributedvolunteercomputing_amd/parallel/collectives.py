@@ -24,6 +24,9 @@ The reductions of the hand-written algorithms run in a HIP kernel (``axpy_bf16``
 GPU buffers. All functions SUM in place; the caller applies the 1/P scale (fused into the
 local-SGD apply kernel).
 
+``robust_mean_`` is the exception: it runs ``direct``'s exchange with a coordinate-wise trimmed
+mean (ops/robust.py) in the middle and leaves the MEAN in the buffer.
+
 No reference analog: the reference has no collectives.
 """
 from __future__ import annotations
@@ -31,6 +34,7 @@ from __future__ import annotations
 import torch
 
 from .. import ops
+from ..ops import robust
 from .peer_group import PeerGroup
 
 ALGOS = ("rccl", "rs_ag", "butterfly", "ring", "direct")
@@ -210,3 +214,43 @@ def _direct(t, group):
     if buf is not t:
         t.copy_(buf[:n])
     return t
+
+
+def robust_mean_(t: torch.Tensor, group: PeerGroup, trim: int, live_ranks=None) -> torch.Tensor:
+    """Coordinate-wise trimmed mean of `t` over the group, in place: `direct`'s exchange (the same
+    padding, splits and two all-to-alls) with the trimmed mean of ops/robust.py as the middle step.
+    Unlike ``allreduce_sum_`` the buffer ends up holding the aggregate itself. `live_ranks`: the
+    ranks that vote (default all); the others send their buffer and receive the result like everyone.
+    Returns counts (int64 [P], identical on every rank): per rank, how many of its elements were
+    trimmed over the whole buffer."""
+    if group is None or group.size == 1:
+        P, r = 1, 0
+    else:
+        P, r = group.size, group.rank
+    mask = robust.mask_of(live_ranks, P)
+    n = t.numel()
+    L = _pad_len(n, P, 8 if t.dtype == torch.bfloat16 else 1)
+    buf = _padded(t, L)
+    m = L // P
+    split = [m] * P
+    counts = torch.zeros(P, dtype=torch.int64, device=buf.device)
+    if P == 1:
+        ops.trimmed_reduce_bcast_bf16(buf, None, buf, 1, trim, mask, counts)
+    else:
+        recv = torch.empty_like(buf)  # [P, m]: row j = peer j's copy of MY shard
+        group.alltoall_(recv, buf, split, split)
+        mine = buf[r * m : (r + 1) * m]
+        ops.trimmed_reduce_bcast_bf16(recv, recv, mine, P, trim, mask, counts)  # recv reused as the send buffer
+        group.alltoall_(buf, recv, split, split)
+        counts = counts.to(group.device if group.backend == "nccl" else "cpu")
+        group.allreduce_(counts)
+    if L != n:
+        # every voter's padding is +0, a tie that goes to the row: its f lowest and f highest voters
+        # were "trimmed" there, which says nothing about them
+        _, f, _ = robust.trim_plan(P, trim, mask)
+        voters = [k for k in range(P) if (mask >> k) & 1]
+        for k in (voters[:f] + voters[len(voters) - f:]) if f else ():
+            counts[k] -= L - n
+    if buf is not t:
+        t.copy_(buf[:n])
+    return counts

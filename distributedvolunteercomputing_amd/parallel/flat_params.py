@@ -147,20 +147,32 @@ class FlatBuffers:
     def names(self):
         return [qn for _, _, qn, *_ in self.entries]
 
-    def averaged(self, group):
+    def averaged(self, group, aggregate: str = "mean", trim: int = 1, live_ranks=None):
         """The mean over the group's peers as a new fp32 vector (None when there is nothing to
         average). The live buffers are not touched: an elastic round loads the result only after
-        its verdict is `commit`, so an aborted round leaves every peer's buffers as they were."""
+        its verdict is `commit`, so an aborted round leaves every peer's buffers as they were.
+        aggregate "trimmed" / "median": the coordinate-wise trimmed mean of ops/robust.py over
+        `live_ranks` (default all) instead: the vectors are all-gathered and every peer applies the
+        fp32 reference (a few hundred KB: no kernel needed)."""
         if not self.entries or group is None or group.size == 1:
             return None
         v = self.as_fp32()
         dev = group.device if group.backend == "nccl" else "cpu"
         v = v.to(dev)
+        if aggregate != "mean":
+            from ..ops import robust
+
+            P = group.size
+            mask = robust.mask_of(live_ranks, P)
+            allv = torch.empty(P * v.numel(), dtype=torch.float32, device=v.device)
+            group.all_gather_(allv, v)
+            trim = robust.effective_trim(aggregate, trim, bin(mask).count("1"))
+            return robust.trimmed_mean_reference(allv.view(P, -1), trim, mask)[0]
         group.allreduce_(v)
         return v.div_(group.size)
 
-    def average_(self, group):
+    def average_(self, group, aggregate: str = "mean", trim: int = 1, live_ranks=None):
         """Mean over the group's peers, loaded into the live buffers (non-elastic callers)."""
-        v = self.averaged(group)
+        v = self.averaged(group, aggregate, trim, live_ranks)
         if v is not None:
             self.load_fp32(v)

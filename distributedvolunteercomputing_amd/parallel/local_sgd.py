@@ -9,6 +9,8 @@ Every H steps (`sync`):
   membership round (elastic only) -> lsgd_delta kernel (bf16 pseudo-gradient)
   -> [compression: top-k+EF, PowerSGD or q8+EF] -> all-reduce SUM over live peers
   -> lsgd_apply kernel (average + optional outer Nesterov momentum, writes anchor/master/param).
+With ``aggregate="trimmed" | "median"`` the all-reduce SUM is replaced by a coordinate-wise trimmed
+mean over the same exchange (collectives.robust_mean_), which survives peers that send wrong numbers.
 
 Reference analog: the chunk (100 frames) is the reference's unit of independent work
 (worker.py:16, server.py:77-91); here the unit is H optimizer steps.
@@ -22,7 +24,8 @@ import torch
 
 from .. import ops
 from ..utils.trace import NULL_TRACER
-from .collectives import allreduce_sum_
+from ..ops.robust import AGGREGATES, effective_trim
+from .collectives import allreduce_sum_, robust_mean_
 from .flat_params import FlatBuffers, FlatParams
 from .peer_group import PeerFailure
 
@@ -46,6 +49,21 @@ class LocalSGDConfig:
     # fp32: m and v in fp32 (12 B/param with the master) | compact: fp8 m and fp16 v with one exponent
     # per 32 elements (7.06 B/param; ops/optim.py CompactState); checkpoints hold fp32 either way
     opt_state: str = "fp32"
+    # how the peers' pseudo-gradients become one: mean | trimmed | median. The robust rules
+    # (ops/robust.py) drop the `trim` lowest and highest values of every coordinate (median: all but
+    # the middle one or two), so up to `trim` peers per coordinate may send anything, NaN included
+    aggregate: str = "mean"
+    trim: int = 1
+
+    def __post_init__(self):
+        check_aggregate(self.aggregate, self.trim)
+
+
+def check_aggregate(aggregate, trim):
+    if aggregate not in AGGREGATES:
+        raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
+    if not isinstance(trim, int) or trim < 0:
+        raise ValueError(f"trim must be an integer >= 0, got {trim!r}")
 
 
 @dataclass
@@ -70,6 +88,11 @@ class LocalSGDTrainer:
         self.master = self.flat.param.float()
         if cfg.opt_state not in ("fp32", "compact"):
             raise ValueError(f"opt_state must be 'fp32' or 'compact', got {cfg.opt_state!r}")
+        check_aggregate(cfg.aggregate, cfg.trim)  # again: the config is mutable after its own check
+        # fault injection (tests, `train --byzantine`): called on self.delta after lsgd_delta, before the collective
+        self.delta_hook = None
+        self.trim_share = None  # robust rules: per rank, the share of its elements trimmed in the last round
+        self._trim_clip_logged = False
         self.cstate = None  # compact mode: the moments live here and self.m / self.v are None
         if cfg.opt_state == "compact":
             ops.check_compact_betas(cfg.betas)
@@ -172,7 +195,7 @@ class LocalSGDTrainer:
         if self.membership is None:
             res = self._reduce(())
             self._apply(res)
-            self.buffers.average_(self.group)
+            self.buffers.average_(self.group, self.cfg.aggregate, self.cfg.trim)
         else:
             self._sync_elastic()
         self.sync_count += 1
@@ -200,7 +223,7 @@ class LocalSGDTrainer:
                     self._dev_sync()
                     t3 = time.perf_counter()
                     res = self._reduce(newcomers)
-                    bufs = self.buffers.averaged(grp)
+                    bufs = self.buffers.averaged(grp, self.cfg.aggregate, self.cfg.trim, self._voters(grp, newcomers))
                     self._dev_sync()
                     t4 = time.perf_counter()
                 self._adopt(adopted)  # nothing is applied before the verdict is `commit`
@@ -234,9 +257,23 @@ class LocalSGDTrainer:
     def _reduce(self, newcomers=()):
         """Pseudo-gradient + collective. Returns what `_apply` needs; touches no model state."""
         g = self.group
+        c = self.cfg
+        robust = c.aggregate != "mean"
+        if robust:
+            check_aggregate(c.aggregate, c.trim)
+            if self.compressor is not None:
+                raise ValueError(f"aggregate={c.aggregate!r} cannot be combined with a compressor: the robust "
+                                 "rules need every peer's uncompressed pseudo-gradient")
+            if c.algo != "direct":
+                raise ValueError(f"aggregate={c.aggregate!r} runs over the 'direct' exchange only, got "
+                                 f"algo={c.algo!r}")
         if g is None or g.size == 1:
             return None
         ops.lsgd_delta(self.master, self.anchor, self.delta)
+        if self.delta_hook is not None:
+            self.delta_hook(self.delta)
+        if robust:
+            return self._reduce_robust(g, newcomers)
         contributors = max(1, g.size - len(newcomers))  # newcomers hold delta == 0
         if self.compressor is not None:
             avg = self.compressor.allreduce_mean(self.delta, g)
@@ -249,6 +286,35 @@ class LocalSGDTrainer:
             self._dev_sync()
             self.reduce_log.append(((time.perf_counter() - t0) * 1e3, self.delta.numel() * self.delta.element_size()))
         return self.delta, 1.0 / contributors
+
+    @staticmethod
+    def _voters(g, newcomers):
+        """Ranks of `g` that hold a trained model: everyone but the newcomers, whose all-zero
+        pseudo-gradient (and untrained buffers) must not vote. None: all ranks."""
+        if not newcomers:
+            return None
+        live = [i for i, m in enumerate(g.members) if m not in newcomers]
+        return live or None  # nobody holds a model yet: every delta is zero, everyone may vote
+
+    def _reduce_robust(self, g, newcomers):
+        """The averaging round under a robust rule: the trimmed mean itself ends up in self.delta."""
+        c = self.cfg
+        live = self._voters(g, newcomers)
+        K = g.size if live is None else len(live)
+        trim = effective_trim(c.aggregate, c.trim, K)
+        if trim > (K - 1) // 2 and not self._trim_clip_logged:
+            self._trim_clip_logged = True
+            print(f"[local-sgd] trim={trim} clipped to {(K - 1) // 2}: only {K} peers vote "
+                  f"(a trimmed mean needs K >= 2 trim + 1)", flush=True)
+        if self.time_reduce:
+            self._dev_sync()
+            t0 = time.perf_counter()
+        counts = robust_mean_(self.delta, g, trim, live)
+        if self.time_reduce:
+            self._dev_sync()
+            self.reduce_log.append(((time.perf_counter() - t0) * 1e3, self.delta.numel() * self.delta.element_size()))
+        self.trim_share = (counts.double() / self.delta.numel()).tolist()
+        return self.delta, 1.0
 
     def _apply(self, res, bufs=None):
         if bufs is not None:
@@ -366,7 +432,7 @@ class LocalSGDTrainer:
                     dev_sync()
                     t3 = time.perf_counter()
                     res = self._reduce(newcomers)
-                    bufs = self.buffers.averaged(grp)
+                    bufs = self.buffers.averaged(grp, self.cfg.aggregate, self.cfg.trim, self._voters(grp, newcomers))
                     dev_sync()
                     t4 = time.perf_counter()
                 self._adopt(adopted)

@@ -157,6 +157,37 @@ void q8_reduce(at::Tensor recv, int64_t P, int64_t m, double avg_scale, at::Tens
   vcx_q8_reduce(recv.data_ptr<uint8_t>(), (int)P, m, (float)avg_scale, out_record.data_ptr<uint8_t>(), cur_stream());
 }
 
+// The robust sibling of q8_reduce: out_record = one record of the trimmed mean (ops/robust.py) over the rows of
+// live_mask; elements at or beyond `valid` do not vote. counts: int64 [P], nonfinite: int64 [1], both optional.
+// Everything is checked here, before the launcher's own checks, so a refused call leaves every output unwritten.
+void q8_trimmed_reduce(at::Tensor recv, int64_t P, int64_t m, int64_t trim, int64_t live_mask, int64_t valid,
+                       at::Tensor out_record, std::optional<at::Tensor> counts, std::optional<at::Tensor> nonfinite) {
+  CHK(recv);
+  CHK(out_record);
+  TORCH_CHECK(P >= 1 && P <= 16, "q8_trimmed_reduce: P must be in 1..16, got ", P);
+  TORCH_CHECK(live_mask > 0 && (live_mask >> P) == 0,
+              "q8_trimmed_reduce: live_mask must name at least one of the P rows and no other, got ", live_mask);
+  TORCH_CHECK(trim >= 0, "q8_trimmed_reduce: trim must be >= 0");
+  check_q8(m, m, 1, out_record, "q8_trimmed_reduce");
+  TORCH_CHECK(valid >= 0 && valid <= m, "q8_trimmed_reduce: valid must be in 0..m, got ", valid);
+  TORCH_CHECK(recv.scalar_type() == at::kByte && recv.numel() >= P * (m + m / 32),
+              "q8_trimmed_reduce: recv must hold P records");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(recv.data_ptr()) & 15) == 0,
+              "q8_trimmed_reduce: recv must be 16-byte aligned");
+  TORCH_CHECK(out_record.get_device() == recv.get_device(), "q8_trimmed_reduce: out_record must be on recv's device");
+  auto counter = [&](const std::optional<at::Tensor>& t, int64_t len, const char* what) -> int64_t* {
+    if (!t.has_value()) return nullptr;
+    TORCH_CHECK(t->is_cuda() && t->get_device() == recv.get_device() && t->numel() == len && t->is_contiguous() &&
+                    t->scalar_type() == at::kLong,
+                "q8_trimmed_reduce: ", what, " must hold ", len, " int64 on recv's device");
+    return t->data_ptr<int64_t>();
+  };
+  int64_t* c = counter(counts, P, "counts");
+  int64_t* nf = counter(nonfinite, 1, "nonfinite");
+  vcx_q8_trimmed_reduce(recv.data_ptr<uint8_t>(), (int)P, m, (int)std::min<int64_t>(trim, 16), (uint32_t)live_mask,
+                        valid, out_record.data_ptr<uint8_t>(), c, nf, cur_stream());
+}
+
 // records: P records covering L elements; out: bf16 [n], the first n decoded values
 void q8_decode(at::Tensor records, int64_t L, int64_t P, at::Tensor out) {
   CHK(records);
@@ -172,6 +203,10 @@ void vcx_register_compress(pybind11::module& m) {
   m.def("q8_encode", &q8_encode);
   m.def("q8_reduce", &q8_reduce);
   m.def("q8_decode", &q8_decode);
+  m.def("q8_trimmed_reduce", &q8_trimmed_reduce, pybind11::arg("recv"), pybind11::arg("P"), pybind11::arg("m"),
+        pybind11::arg("trim"), pybind11::arg("live_mask"), pybind11::arg("valid"), pybind11::arg("out_record"),
+        pybind11::arg("counts") = pybind11::none(), pybind11::arg("nonfinite") = pybind11::none());
+  m.def("q8_trimmed_reduce_max_blocks", &vcx_q8_trimmed_reduce_max_blocks);
   m.def("q8_block", &vcx_q8_block);
   m.def("topk_ef", &topk_ef);
   m.def("scatter_add", &scatter_add);

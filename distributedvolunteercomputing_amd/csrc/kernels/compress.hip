@@ -20,8 +20,13 @@
 // stage through a device-side descriptor table (grouped kernels).
 //
 // q8: 8-bit quantisation in blocks of 128 with one fp32 scale each and error feedback: three
-// streaming kernels (encode, reduce on the shard owner, decode), described at their section below.
+// streaming kernels (encode, reduce on the shard owner, decode), described at their section below,
+// and the robust reduce (the trimmed mean of ops/robust.py over the decoded records) that takes the
+// place of the rank-order sum under --aggregate trimmed | median.
 #include "vcx_common.h"
+
+#include <stdexcept>
+#include <string>
 
 namespace vcx {
 
@@ -881,6 +886,125 @@ __global__ void __launch_bounds__(256) q8_decode_kernel(const uint8_t* __restric
   }
 }
 
+// The robust sibling of q8_reduce_kernel: the rank-order sum becomes the coordinate-wise trimmed mean
+// of ops/robust.py over the decoded records (parallel/compression.py, reduce_robust, holds the torch
+// definition; the two agree bit for bit). Per element of the shard, over the rows named by `live`:
+//   * dec = float(code) * scale, one fp32 multiply on whatever bytes the record holds; a NaN product
+//     counts as the canonical +NaN 0x7FC00000 (the sign and payload of a NaN that an operation makes
+//     differ between processors: 0 * Inf is 0xFFC00000 on x86 and 0x7FC00000 here).
+//   * order key s = pattern ^ (negative ? 0xFFFFFFFF : 0x80000000), ties go to the row. An fp32 key
+//     and a row do not fit one dword, so nothing is sorted: for every pair j < k, row j precedes row k
+//     iff s_j <= s_k, and a row's rank is the number of rows that precede it. A dead row takes the key
+//     0xFFFFFFFF, above every live key, so the K live rows hold the ranks 0 .. K-1.
+//   * kept iff f <= rank <= K-1-f; result = (sum of the kept values, ascending row order, from +0) *
+//     inv, no fused multiply-add; a non-finite result becomes +0 and adds 1 to `nonfinite`.
+//   * elements at or beyond `valid` (the padding of the last shards) do not vote: result +0, no count.
+//   * counts[k] += 1 for every live row k that voted and was not kept.
+// The results are quantised by the codec of the other q8 kernels into one record. Same work split as
+// q8_reduce_kernel; every lane of a wave, lanes past the end included, reaches the cross-lane maximum.
+// PP: P padded to a power of two; rows outside `live` (P..PP-1 among them) are never read.
+constexpr int Q8_TRIMMED_MAX_BLOCKS = 2048;  // the grid cap: a shard above 2048 * 256 * 8 elements takes a second trip
+
+template <int PP>
+__global__ void __launch_bounds__(256) q8_trimmed_reduce_kernel(const uint8_t* __restrict__ recv, uint32_t bps,
+                                                                 uint32_t valid, int f, int K, uint32_t live,
+                                                                 float inv, uint8_t* __restrict__ out,
+                                                                 unsigned long long* __restrict__ counts,
+                                                                 unsigned long long* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  __shared__ uint32_t wave_cnt[4][PP + 1];
+  const uint32_t units = bps * 16u;
+  const int64_t rec = (int64_t)bps * Q8_REC, soff = (int64_t)bps * Q8_BLOCK;
+  const uint32_t span = (uint32_t)(K - 1 - 2 * f);
+  uint32_t cnt[PP];  // elements of this thread at which the row voted and was not kept (dead rows: dropped below)
+#pragma unroll
+  for (int k = 0; k < PP; ++k) cnt[k] = 0;
+  uint32_t bad = 0;
+  for (uint32_t base = blockIdx.x * 256u; base < units; base += gridDim.x * 256u) {
+    const uint32_t u = base + threadIdx.x;
+    const bool in_range = u < units;
+    u32x2 w[PP];
+    float sc[PP];
+#pragma unroll
+    for (int k = 0; k < PP; ++k) {
+      w[k] = u32x2{0u, 0u};
+      sc[k] = 0.f;
+      if (in_range && ((live >> k) & 1u)) {
+        w[k] = *(const u32x2_a4*)(recv + k * rec + (int64_t)u * 8);
+        sc[k] = *(const float*)(recv + k * rec + soff + (int64_t)(u >> 4) * 4);
+      }
+    }
+    float res[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool votes = in_range && u * 8u + j < valid;  // below 2^31, as m is
+      uint32_t val[PP], s[PP], rank[PP];
+#pragma unroll
+      for (int k = 0; k < PP; ++k) {
+        const float d = q8_code(w[k][j >> 2], j & 3) * sc[k];
+        val[k] = d != d ? 0x7FC00000u : __float_as_uint(d);
+        // a dead row (w = 0, sc = 0: val = +0) takes the key 0xFFFFFFFF, above every live key: live keys end at
+        // +NaN, 0xFFC00000, now that NaN has one pattern. The mask is wave-uniform and folds into the sign flip
+        const uint32_t flip = 0x80000000u | (((live >> k) & 1u) - 1u);
+        s[k] = val[k] ^ ((uint32_t)((int32_t)val[k] >> 31) | flip);
+        rank[k] = (uint32_t)(PP - 1 - k - f);  // rank - f, modulo 2^32, once the rows after k have had their say
+      }
+#pragma unroll
+      for (int k = 1; k < PP; ++k) {
+#pragma unroll
+        for (int i = 0; i < k; ++i) {
+          const uint32_t first = s[i] <= s[k] ? 1u : 0u;  // row i precedes row k
+          rank[k] += first;
+          rank[i] -= first;
+        }
+      }
+      float t = 0.f;
+#pragma unroll
+      for (int k = 0; k < PP; ++k) {
+        const bool kept = rank[k] <= span;  // f <= rank <= K - 1 - f; a dead row's rank is K or more
+        t += kept ? __uint_as_float(val[k]) : 0.f;  // + (+0) leaves a sum that started at +0 unchanged
+        cnt[k] += (votes && !kept) ? 1u : 0u;
+      }
+      const float r = t * inv;
+      const bool finite = (__float_as_uint(r) & 0x7F800000u) != 0x7F800000u;
+      bad += (votes && !finite) ? 1u : 0u;
+      res[j] = (votes && finite) ? r : 0.f;
+      // one element at a time: left to itself the scheduler interleaves the eight elements' comparisons, whose lane
+      // masks (120 pairs of scalar registers per element at 16 rows) then spill by the thousand
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(res[j]));
+    amax = q8_group_max(amax);
+    float scale, dec[8];
+    const u32x2 o = q8_quantise8(res, amax, scale, dec);
+    if (!in_range) continue;
+    *(u32x2_a4*)(out + (int64_t)u * 8) = o;
+    if ((u & 15u) == 0) *(float*)(out + soff + (int64_t)(u >> 4) * 4) = scale;
+  }
+  if (counts || nonfinite) {  // registers -> wave -> block (LDS) -> one global atomic per live row per block
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k <= PP; ++k) {
+      uint32_t c = k < PP ? cnt[k < PP ? k : 0] : bad;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+      if (lane == 0) wave_cnt[wid][k] = c;
+    }
+    __syncthreads();
+    const int k = threadIdx.x;
+    if (k <= PP) {
+      const uint32_t c = wave_cnt[0][k] + wave_cnt[1][k] + wave_cnt[2][k] + wave_cnt[3][k];
+      if (k < PP) {
+        if (counts && ((live >> k) & 1u) && c) atomicAdd(counts + k, (unsigned long long)c);
+      } else if (nonfinite && c) {
+        atomicAdd(nonfinite, (unsigned long long)c);
+      }
+    }
+  }
+}
+
 }  // namespace vcx
 
 // ====================================================================================== launchers
@@ -1001,6 +1125,44 @@ void vcx_q8_reduce(const uint8_t* recv, int P, int64_t m, float avg_scale, uint8
   hipLaunchKernelGGL(q8_reduce_kernel, dim3(stream_grid(m / 8, 256, 2048)), dim3(256), 0, s, recv, P, bps, avg_scale,
                      out_record);
 }
+
+// A call the kernel cannot take raises before anything is launched.
+void vcx_q8_trimmed_reduce(const uint8_t* recv, int P, int64_t m, int trim, uint32_t live_mask, int64_t valid,
+                           uint8_t* out_record, int64_t* counts, int64_t* nonfinite, hipStream_t s) {
+  const std::string who = "q8_trimmed_reduce";
+  if (P < 1 || P > 16) throw std::invalid_argument(who + ": P must be in 1..16, got " + std::to_string(P));
+  if (live_mask == 0 || (live_mask >> P) != 0)
+    throw std::invalid_argument(who + ": live_mask must name at least one of the P rows and no other");
+  if (m <= 0 || m % Q8_BLOCK != 0 || m >= INT32_MAX)
+    throw std::invalid_argument(who + ": m must be a positive multiple of 128 below 2^31, got " + std::to_string(m));
+  if (valid < 0 || valid > m)
+    throw std::invalid_argument(who + ": valid must be in 0..m, got " + std::to_string(valid));
+  if (trim < 0) throw std::invalid_argument(who + ": trim must be >= 0");
+  if (!recv || ((uintptr_t)recv & 15)) throw std::invalid_argument(who + ": recv must be 16-byte aligned");
+  if (!out_record || ((uintptr_t)out_record & 3))
+    throw std::invalid_argument(who + ": out_record must be 4-byte aligned");
+  if (((uintptr_t)counts | (uintptr_t)nonfinite) & 7)
+    throw std::invalid_argument(who + ": counts and nonfinite must be 8-byte aligned");
+  const int K = __builtin_popcount(live_mask);
+  const int f = trim < (K - 1) / 2 ? trim : (K - 1) / 2;
+  const float inv = (float)(1.0 / (double)(K - 2 * f));  // the fp32 value ops/robust.py trim_plan computes
+  const uint32_t bps = (uint32_t)(m / Q8_BLOCK);
+  const dim3 grid(stream_grid(m / 8, 256, Q8_TRIMMED_MAX_BLOCKS)), block(256);
+#define VCX_Q8T_LAUNCH(PP)                                                                                       \
+  hipLaunchKernelGGL(q8_trimmed_reduce_kernel<PP>, grid, block, 0, s, recv, bps, (uint32_t)valid, f, K, live_mask, \
+                     inv, out_record, (unsigned long long*)counts, (unsigned long long*)nonfinite)
+  if (P <= 2)
+    VCX_Q8T_LAUNCH(2);
+  else if (P <= 4)
+    VCX_Q8T_LAUNCH(4);
+  else if (P <= 8)
+    VCX_Q8T_LAUNCH(8);
+  else
+    VCX_Q8T_LAUNCH(16);
+#undef VCX_Q8T_LAUNCH
+}
+
+int vcx_q8_trimmed_reduce_max_blocks() { return Q8_TRIMMED_MAX_BLOCKS; }
 
 void vcx_q8_decode(const uint8_t* records, int64_t n, int64_t L, int P, void* out_bf16, hipStream_t s) {
   const uint32_t bps = (uint32_t)(L / P / Q8_BLOCK);

@@ -29,6 +29,14 @@ void vcx_ef_accum(const void* g, float* e, int64_t n, hipStream_t s);
 void vcx_q8_encode(const void* g, int g_is_bf16, float* e, int64_t n, int64_t L, int P, uint8_t* wire, hipStream_t s);
 // recv: P records of one shard; out_record = encode(avg_scale * sum over p = 0..P-1 of decoded record p)
 void vcx_q8_reduce(const uint8_t* recv, int P, int64_t m, float avg_scale, uint8_t* out_record, hipStream_t s);
+// recv: P records of one shard; out_record = encode(trimmed mean over the rows of live_mask of the decoded
+// records), the rule of ops/robust.py with f = min(trim, (K - 1) / 2); elements at or beyond `valid` do not
+// vote and encode as +0; a non-finite result becomes +0 and adds 1 to *nonfinite. counts (P int64, += the
+// elements at which a live row was trimmed) and nonfinite (1 int64) may be null. Throws
+// std::invalid_argument, before anything is launched, for a call the kernel cannot take.
+void vcx_q8_trimmed_reduce(const uint8_t* recv, int P, int64_t m, int trim, uint32_t live_mask, int64_t valid,
+                           uint8_t* out_record, int64_t* counts, int64_t* nonfinite, hipStream_t s);
+int vcx_q8_trimmed_reduce_max_blocks();  // the launcher's grid cap (blocks of 256 lanes, 8 elements per lane)
 // records: P records (L elements); writes the first n decoded values as bf16
 void vcx_q8_decode(const uint8_t* records, int64_t n, int64_t L, int P, void* out_bf16, hipStream_t s);
 int vcx_q8_block();

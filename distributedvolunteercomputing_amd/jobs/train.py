@@ -90,6 +90,15 @@ def _fill_nan(d):
 BYZANTINE = {"none": None, "nan": _fill_nan, "flip": lambda d: d.mul_(-1.0), "scale": lambda d: d.mul_(1e4)}
 
 
+def nan_scales(records):
+    """--byzantine nan under --compression q8: NaN into every scale of the peer's own wire records (uint8
+    [P, record]: m codes, then m / 128 fp32 scales). A NaN pseudo-gradient through the codec is undefined and
+    differs between CPU and GPU; a NaN scale is what a faulty peer can actually put on the wire."""
+    m = records.shape[1] * 32 // 33
+    nan = torch.tensor([0x00, 0x00, 0xC0, 0x7F], dtype=torch.uint8, device=records.device)  # 0x7FC00000, little endian
+    records[:, m:] = nan.repeat((records.shape[1] - m) // 4)
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(prog="train", description=__doc__.splitlines()[0])
     ap.add_argument("--model", default="gpt2")
@@ -126,7 +135,8 @@ def parse(argv=None):
     ap.add_argument("--drop-at", type=int, default=-1, help="fault injection: crash this peer at that step")
     ap.add_argument("--byzantine", default="none", choices=list(BYZANTINE),
                     help="fault injection: this peer stays alive and sends a wrong pseudo-gradient to every "
-                         "averaging round (nan: all NaN, flip: times -1, scale: times 1e4)")
+                         "averaging round (nan: all NaN, with --compression q8 NaN in every scale of its wire records; "
+                         "flip: times -1, scale: times 1e4)")
     ap.add_argument("--aggregate", default="mean", choices=["mean", "trimmed", "median"],
                     help="localsgd: how the peers' pseudo-gradients become one. trimmed / median: coordinate-wise "
                          "trimmed mean, survives up to --trim wrong peers per coordinate")
@@ -201,9 +211,13 @@ def main(argv=None):
         cfg = LocalSGDConfig(lr=a.lr, H=a.H, algo=a.algo or "direct", outer_lr=a.outer_lr,
                              outer_momentum=a.outer_momentum, opt_state=a.opt_state,
                              comm_dtype=torch.bfloat16 if cuda else torch.float32,
-                             aggregate=a.aggregate, trim=a.trim)
+                             aggregate=a.aggregate, trim=a.trim,
+                             robust_q8=a.compression == "q8" and a.aggregate != "mean")
         tr = LocalSGDTrainer(model, cfg, group=group, membership=membership, device=device)
-        tr.delta_hook = BYZANTINE[a.byzantine]
+        if a.compression == "q8" and a.byzantine == "nan":
+            tr.wire_hook = nan_scales
+        else:
+            tr.delta_hook = BYZANTINE[a.byzantine]
     else:
         from ..parallel.zero import ShardedConfig, ShardedDPTrainer
 
@@ -281,6 +295,8 @@ def main(argv=None):
                    "gen": membership.gen if membership else 0}
             if getattr(out, "synced", False) and getattr(tr, "trim_share", None) is not None:
                 rec["trim_share"] = [round(s, 4) for s in tr.trim_share]  # per rank, of the round just done
+                if getattr(tr, "nonfinite_share", None) is not None:
+                    rec["nonfinite_share"] = round(tr.nonfinite_share, 6)
             t_last = now
             print(json.dumps(rec), flush=True)
             if log:

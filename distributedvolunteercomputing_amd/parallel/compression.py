@@ -10,7 +10,9 @@
 * ``Quant8Compressor`` — 8-bit quantisation in blocks of 128 with one fp32 scale each and error
   feedback (1.03 B per element, any model, nothing to tune), moved like the ``direct``
   all-reduce: all-to-all of the codes, a fused dequantise-sum-requantise on the shard owner,
-  all-gather of the averaged codes.
+  all-gather of the averaged codes. It is the one compressor that combines with the robust rules
+  (``allreduce_robust``): the shard owner holds every peer's record before anything is summed, so the
+  sum becomes the coordinate-wise trimmed mean of ops/robust.py over the decoded records.
 
 All expose ``allreduce_mean(buf_bf16, group) -> averaged bf16 buffer`` so they plug into
 ``LocalSGDTrainer`` (compressing the pseudo-gradient) and the sharded data-parallel trainer
@@ -24,6 +26,7 @@ import math
 import numpy as np
 import torch
 
+from ..ops import robust
 from ..ops._lib import native, use_native
 from .flat_params import FlatParams
 
@@ -148,7 +151,9 @@ class Quant8Compressor:
     all-to-all of the records -> ``reduce`` on the shard owner (sum of the decoded records in rank
     order, times 1/P, quantised again into one record) -> all-gather of that record -> ``decode``
     into a bf16 buffer. The second quantisation has no error feedback: its residual is at most
-    half a code unit of the averaged block and identical on every peer.
+    half a code unit of the averaged block and identical on every peer. ``allreduce_robust`` is the
+    same round with ``reduce_robust`` in the middle: the trimmed mean over the peers' decoded records
+    in place of their sum, plus one small all-reduce of the trimmed / non-finite counters.
 
     Layout: the n elements are padded to L = ceil(n / (128 P)) 128 P (no padded copy is made: the
     kernels bounds-check), shard j is the elements [j m, (j + 1) m) with m = L / P, and its record
@@ -166,6 +171,9 @@ class Quant8Compressor:
         self._bufs = {}  # (P, name) -> uint8 buffer, see _buf
         self.out = None  # bf16 [n], allocated on first use
         self.bytes_sent = 0
+        # fault injection (LocalSGDTrainer.wire_hook): called on this peer's own wire records
+        # (uint8 [P, record]) at the end of every encode
+        self.wire_hook = None
 
     @property
     def bytes_per_element(self) -> float:
@@ -199,7 +207,7 @@ class Quant8Compressor:
         wire = self._buf(P, "wire")
         if use_native(g):
             native().q8_encode(g.contiguous(), self.e, L, P, wire)
-            return wire
+            return self._hooked(wire, P)
         v = torch.zeros(L, dtype=torch.float32, device=g.device)
         v[: self.n] = self.e + g.float()
         q, scale = q8_quantise(v.view(-1, self.BLOCK))
@@ -208,6 +216,11 @@ class Quant8Compressor:
         w = wire.view(P, rec)
         w[:, :m] = q.view(P, m).view(torch.uint8)
         w[:, m:] = scale.view(P, m // self.BLOCK).view(torch.uint8)
+        return self._hooked(wire, P)
+
+    def _hooked(self, wire: torch.Tensor, P: int) -> torch.Tensor:
+        if self.wire_hook is not None:
+            self.wire_hook(wire.view(P, -1))
         return wire
 
     @classmethod
@@ -237,6 +250,64 @@ class Quant8Compressor:
         record[:m] = q2.view(-1).view(torch.uint8)
         record[m:] = s2.view(torch.uint8)
         return record
+
+    def reduce_robust(self, recv: torch.Tensor, P: int, trim: int, live_mask: int | None, valid: int,
+                      counts: torch.Tensor | None = None, nonfinite: torch.Tensor | None = None) -> torch.Tensor:
+        """The robust sibling of ``reduce``: one record of the coordinate-wise trimmed mean
+        (ops/robust.py) of the P peers' decoded records of this peer's shard. The definition, which
+        the HIP kernel q8_trimmed_reduce matches bit for bit:
+
+        * dec[p][i] = float(code) * scale, one fp32 multiply, on whatever bytes a peer sent: nothing
+          is sanitised. A NaN product is taken as the canonical +NaN 0x7FC00000, because the sign and
+          payload of a NaN that an operation produces differ between processors (0 * Inf is
+          0xFFC00000 on x86, 0x7FC00000 on gfx950); a non-finite value is an extreme of the order
+          either way and is trimmed first.
+        * res, counts = trimmed_mean_reference(dec, f, live_mask) on fp32 rows.
+        * a non-finite res[i] (more than f bad voters, or an overflowing sum) becomes +0 and adds 1
+          to `nonfinite`: no update for that coordinate, and the round says so.
+        * elements at or beyond `valid` (the padding beyond n) do not vote: result +0, no count.
+        * res is quantised by the codec of the other stages (``q8_quantise``).
+
+        `counts` (int64 [P]) and `nonfinite` (int64 [1]) are added to if given."""
+        L, m, rec = self.layout(P)
+        live_mask = robust.full_mask(P) if live_mask is None else int(live_mask)
+        K, f, _ = robust.trim_plan(P, trim, live_mask)
+        valid = int(valid)
+        if not 0 <= valid <= m:
+            raise ValueError(f"reduce_robust: valid must be in 0..{m}, got {valid}")
+        if recv.dtype != torch.uint8 or recv.numel() < P * rec:
+            raise ValueError(f"reduce_robust: recv must hold {P} uint8 records of {rec} bytes")
+        for t, k, what in ((counts, P, "counts"), (nonfinite, 1, "nonfinite")):
+            if t is not None and (t.dtype != torch.int64 or t.numel() != k):
+                raise ValueError(f"reduce_robust: {what} must hold {k} int64")
+        record = self._buf(P, "record")
+        if use_native(recv):
+            native().q8_trimmed_reduce(recv, P, m, f, live_mask, valid, record, counts, nonfinite)
+            return record
+        out, c, bad = self.reduce_robust_reference(recv, P, f, live_mask, valid)
+        record.copy_(out)
+        if counts is not None:
+            counts.add_(c.to(counts.device))
+        if nonfinite is not None:
+            nonfinite.add_(bad.to(nonfinite.device))
+        return record
+
+    @classmethod
+    def reduce_robust_reference(cls, recv: torch.Tensor, P: int, trim: int, live_mask: int, valid: int):
+        """The definition of ``reduce_robust`` in torch, on recv's device whichever it is: (record uint8
+        [rec], counts int64 [P], nonfinite int64 scalar) of the P records in `recv`."""
+        rec = recv.numel() // P
+        m = rec * 32 // 33
+        q, scale = cls._unpack(recv[: P * rec], P)
+        dec = (q * scale).view(P, m)[:, :valid]
+        nan = torch.tensor([0x7FC00000], dtype=torch.int32, device=recv.device).view(torch.float32)
+        dec = torch.where(torch.isnan(dec), nan, dec)
+        res, c = robust.trimmed_mean_reference(dec, trim, live_mask)
+        bad = ~torch.isfinite(res)
+        out = torch.zeros(m, dtype=torch.float32, device=recv.device)
+        out[:valid] = torch.where(bad, torch.zeros_like(res), res)
+        q2, s2 = q8_quantise(out.view(-1, cls.BLOCK))
+        return torch.cat([q2.view(-1).view(torch.uint8), s2.view(torch.uint8)]), c, bad.sum()
 
     def decode_f32(self, records: torch.Tensor, P: int) -> torch.Tensor:
         """The decoded fp32 values of the P gathered records, before the bf16 output rounding
@@ -283,6 +354,32 @@ class Quant8Compressor:
         group.all_gather_(gathered, record)
         self.bytes_sent += 2 * (P - 1) * rec  # (P-1)/P of L + L/32 bytes out in each collective
         return self.decode(gathered, P)
+
+    def allreduce_robust(self, g: torch.Tensor, group, trim: int, live_ranks=None):
+        """``allreduce_mean`` with the trimmed mean of ``reduce_robust`` as the middle step: encode ->
+        all-to-all -> reduce_robust -> all-gather -> all-reduce of the counters -> decode. `live_ranks`:
+        the ranks that vote (default all); the others send their records and receive the result like
+        everyone. Returns (avg bf16 [n], counts int64 [P], nonfinite int), the counters summed over
+        the whole buffer and identical on every rank: per rank, the elements at which it was trimmed,
+        and the coordinates whose aggregate was non-finite and came out as 0."""
+        P, r = (1, 0) if group is None else (group.size, group.rank)
+        mask = robust.mask_of(live_ranks, P)
+        robust.trim_plan(P, trim, mask)  # every refusal before e is touched
+        L, m, rec = self.layout(P)
+        valid = min(max(self.n - r * m, 0), m)
+        wire = self.encode(g, P)
+        ctr = torch.zeros(P + 1, dtype=torch.int64, device=self.device)  # counts [P], then nonfinite
+        if P == 1:
+            gathered = self.reduce_robust(wire, 1, trim, mask, valid, ctr[:1], ctr[1:])
+        else:
+            recv, gathered = self._buf(P, "recv"), self._buf(P, "gathered")
+            group.alltoall_(recv, wire, [rec] * P, [rec] * P)
+            record = self.reduce_robust(recv, P, trim, mask, valid, ctr[:P], ctr[P:])
+            group.all_gather_(gathered, record)
+            ctr = ctr.to(group.device if group.backend == "nccl" else "cpu")
+            group.allreduce_(ctr)
+            self.bytes_sent += 2 * (P - 1) * rec + ctr.numel() * ctr.element_size()
+        return self.decode(gathered, P), ctr[:P], int(ctr[P])
 
 
 class PowerSGDCompressor:

@@ -11,6 +11,9 @@ Every H steps (`sync`):
   -> lsgd_apply kernel (average + optional outer Nesterov momentum, writes anchor/master/param).
 With ``aggregate="trimmed" | "median"`` the all-reduce SUM is replaced by a coordinate-wise trimmed
 mean over the same exchange (collectives.robust_mean_), which survives peers that send wrong numbers.
+The robust rules combine with q8 compression (on request: LocalSGDConfig.robust_q8) and with no other: the
+q8 shard owner holds every peer's record of its shard before anything is summed, so its reduce kernel takes
+the trimmed mean of the decoded records instead (Quant8Compressor.allreduce_robust).
 
 Reference analog: the chunk (100 frames) is the reference's unit of independent work
 (worker.py:16, server.py:77-91); here the unit is H optimizer steps.
@@ -26,6 +29,7 @@ from .. import ops
 from ..utils.trace import NULL_TRACER
 from ..ops.robust import AGGREGATES, effective_trim
 from .collectives import allreduce_sum_, robust_mean_
+from .compression import Quant8Compressor
 from .flat_params import FlatBuffers, FlatParams
 from .peer_group import PeerFailure
 
@@ -54,6 +58,12 @@ class LocalSGDConfig:
     # the middle one or two), so up to `trim` peers per coordinate may send anything, NaN included
     aggregate: str = "mean"
     trim: int = 1
+    # let a robust rule run over the q8 exchange (Quant8Compressor.allreduce_robust). Off by default, so a robust
+    # rule with any compressor is refused as before: over q8 the rule does not mean quite what it means on the
+    # uncompressed pseudo-gradient (the aggregate is quantised again, and a coordinate whose aggregate is
+    # non-finite comes out as 0 and is counted in nonfinite_share where the uncompressed rule hands on the NaN),
+    # so the caller says that this is what it wants. `train --compression q8 --aggregate ...` says so
+    robust_q8: bool = False
 
     def __post_init__(self):
         check_aggregate(self.aggregate, self.trim)
@@ -91,7 +101,12 @@ class LocalSGDTrainer:
         check_aggregate(cfg.aggregate, cfg.trim)  # again: the config is mutable after its own check
         # fault injection (tests, `train --byzantine`): called on self.delta after lsgd_delta, before the collective
         self.delta_hook = None
+        # the same for the wire: called on this peer's own q8 records (uint8 [P, record]) after encode
+        self.wire_hook = None
         self.trim_share = None  # robust rules: per rank, the share of its elements trimmed in the last round
+        # robust rules over q8: the share of the coordinates whose aggregate was non-finite (more than `trim`
+        # bad voters, or an overflowing sum) and came out as 0 in the last round
+        self.nonfinite_share = None
         self._trim_clip_logged = False
         self.cstate = None  # compact mode: the moments live here and self.m / self.v are None
         if cfg.opt_state == "compact":
@@ -261,9 +276,17 @@ class LocalSGDTrainer:
         robust = c.aggregate != "mean"
         if robust:
             check_aggregate(c.aggregate, c.trim)
-            if self.compressor is not None:
-                raise ValueError(f"aggregate={c.aggregate!r} cannot be combined with a compressor: the robust "
-                                 "rules need every peer's uncompressed pseudo-gradient")
+            if self.compressor is not None and not isinstance(self.compressor, Quant8Compressor):
+                raise ValueError(f"aggregate={c.aggregate!r} cannot be combined with the "
+                                 f"{type(self.compressor).__name__} compressor: a coordinate-wise rule needs every "
+                                 "peer's own value of every coordinate on the shard owner, and top-k sends a "
+                                 "different set of coordinates from every peer while PowerSGD sums low-rank "
+                                 "factors; q8 is the compressor that works with the robust rules")
+            if self.compressor is not None and not c.robust_q8:
+                raise ValueError(f"aggregate={c.aggregate!r} is combined with the q8 compressor only on request: set "
+                                 "LocalSGDConfig.robust_q8 (the rule then runs on the peers' decoded 8-bit records: "
+                                 "the aggregate is quantised again, and a non-finite coordinate comes out as 0 and "
+                                 "is counted in nonfinite_share)")
             if c.algo != "direct":
                 raise ValueError(f"aggregate={c.aggregate!r} runs over the 'direct' exchange only, got "
                                  f"algo={c.algo!r}")
@@ -272,6 +295,8 @@ class LocalSGDTrainer:
         ops.lsgd_delta(self.master, self.anchor, self.delta)
         if self.delta_hook is not None:
             self.delta_hook(self.delta)
+        if isinstance(self.compressor, Quant8Compressor):
+            self.compressor.wire_hook = self.wire_hook
         if robust:
             return self._reduce_robust(g, newcomers)
         contributors = max(1, g.size - len(newcomers))  # newcomers hold delta == 0
@@ -306,6 +331,11 @@ class LocalSGDTrainer:
             self._trim_clip_logged = True
             print(f"[local-sgd] trim={trim} clipped to {(K - 1) // 2}: only {K} peers vote "
                   f"(a trimmed mean needs K >= 2 trim + 1)", flush=True)
+        if self.compressor is not None:  # q8 (anything else was refused): the trimmed mean of the decoded records
+            avg, counts, nonfinite = self.compressor.allreduce_robust(self.delta, g, trim, live)
+            self.trim_share = (counts.double() / self.delta.numel()).tolist()
+            self.nonfinite_share = nonfinite / self.delta.numel()
+            return avg, 1.0
         if self.time_reduce:
             self._dev_sync()
             t0 = time.perf_counter()

@@ -632,6 +632,40 @@ void trimmed_reduce_bcast_bf16(at::Tensor in, c10::optional<at::Tensor> out, c10
                                 cur_stream());
 }
 
+// Centered clipping (robust.hip), the per-peer sibling of the call above: the same checks, then tau, iters and
+// weights; the workspace (the fp32 centre, the distances' chunk partials, the weights) is allocated here.
+void cclip_reduce_bcast_bf16(at::Tensor in, c10::optional<at::Tensor> out, c10::optional<at::Tensor> mine, int64_t P,
+                             int64_t live_mask, double tau, int64_t iters, c10::optional<at::Tensor> weights) {
+  TORCH_CHECK(in.is_cuda() && in.scalar_type() == at::kBFloat16 && in.is_contiguous(),
+              "cclip_reduce_bcast: in must be a contiguous bf16 GPU tensor");
+  TORCH_CHECK(P >= 1 && P <= 16, "cclip_reduce_bcast: P must be in 1..16, got ", P);
+  TORCH_CHECK(live_mask > 0 && (live_mask >> P) == 0,
+              "cclip_reduce_bcast: live_mask must name at least one of the P rows and no other, got ", live_mask);
+  TORCH_CHECK(tau >= 0.0 && tau <= 3.4028234663852886e38,  // a finite fp32 value; a NaN fails both comparisons
+              "cclip_reduce_bcast: tau must be finite and >= 0 (0: adaptive), got ", tau);
+  TORCH_CHECK(iters >= 1 && iters <= 8, "cclip_reduce_bcast: iters must be in 1..8, got ", iters);
+  const int64_t n = in.numel() / P;
+  TORCH_CHECK(n * P == in.numel() && n % 8 == 0, "cclip_reduce_bcast: numel must be P * n with n % 8 == 0");
+  auto aligned = [](const at::Tensor& t, uintptr_t a) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % a == 0; };
+  TORCH_CHECK(aligned(in, 16), "cclip_reduce_bcast: in must be 16-byte aligned");
+  if (out)
+    TORCH_CHECK(out->is_cuda() && out->get_device() == in.get_device() && out->numel() == in.numel() &&
+                    out->is_contiguous() && out->scalar_type() == at::kBFloat16 && aligned(*out, 16),
+                "cclip_reduce_bcast: out must match in (bf16, same length, 16-byte aligned)");
+  if (mine)
+    TORCH_CHECK(mine->is_cuda() && mine->get_device() == in.get_device() && mine->numel() == n &&
+                    mine->is_contiguous() && mine->scalar_type() == at::kBFloat16 && aligned(*mine, 16),
+                "cclip_reduce_bcast: mine must hold n bf16, 16-byte aligned");
+  if (weights)
+    TORCH_CHECK(weights->is_cuda() && weights->get_device() == in.get_device() && weights->numel() == P &&
+                    weights->is_contiguous() && weights->scalar_type() == at::kFloat,
+                "cclip_reduce_bcast: weights must hold P fp32 on in's device");
+  at::Tensor ws = at::empty({vcx_cclip_workspace_floats((int)P, n)}, in.options().dtype(at::kFloat));
+  vcx_cclip_reduce_bcast_bf16(in.data_ptr(), opt_ptr(out), opt_ptr(mine), (int)P, n, (uint32_t)live_mask, (float)tau,
+                              (int)iters, weights ? weights->data_ptr<float>() : nullptr, ws.data_ptr<float>(),
+                              cur_stream());
+}
+
 void axpy_bf16(at::Tensor src, at::Tensor acc, double scale) {
   CHECK_IN(src, kBF);
   CHECK_IN(acc, kBF);
@@ -1061,6 +1095,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("axpy_bf16", &axpy_bf16);
   m.def("reduce_bcast_bf16", &reduce_bcast_bf16);
   m.def("trimmed_reduce_bcast_bf16", &trimmed_reduce_bcast_bf16);
+  m.def("cclip_reduce_bcast_bf16", &cclip_reduce_bcast_bf16);
+  m.def("cclip_max_workgroups", &vcx_cclip_max_workgroups);
   m.def("gemm_nt_supported", &gemm_nt_supported);
   m.def("gemm_nt_supported_epi", &gemm_nt_supported_epi);
   m.def("gemm_ps_supported", &gemm_ps_supported);

@@ -134,6 +134,281 @@ __global__ void __launch_bounds__(256) trimmed_reduce_bcast_bf16_kernel(const bf
   }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// Centered clipping (cclip): the per-peer rule next to the coordinate-wise one. ops/robust.py holds the definition
+// and the torch reference; these kernels agree with it bit for bit. In short, over the live rows x_i of one shard:
+//   v = float(median rule's result); L times: D_i = sum_j (x_i[j] - v[j])^2 in the fixed order below,
+//   d_i = sqrt(D_i), w_i = d_i <= tau ? 1 : tau / d_i (0 for a non-finite D_i; tau = 0: the (K-1)/2-th smallest
+//   d_i), v += (sum_i w_i (x_i - v)) * inv_K; result = bf16_rne(v).
+// The order of a distance depends on n only. A chunk is 4096 elements = 512 vectors of 8; thread t of the 256 adds
+// the squares of vector t, then of vector 256 + t, in ascending element order from +0 (a vector past the end adds
+// nothing: the sums are never -0). The 256 thread sums are combined pairwise over adjacent indices: the xor
+// butterfly inside a wave (an IEEE add commutes, so both lanes of a pair hold lower + higher), then (w0 + w1) +
+// (w2 + w3). Workgroups stride over whole chunks and write one partial per row and chunk, so nothing depends on the
+// grid; the weights kernel adds the partials in ascending chunk order. 2L + 1 launches on one stream: init,
+// L x (weights, step). No atomics, no fused multiply-add.
+constexpr int CC_CHUNK_VEC = 512;      // vectors of 8 elements per chunk
+constexpr int CC_MAX_BLOCKS = 256 * 8;  // workgroup cap of the init and step passes: more chunks are strided over
+constexpr int CC_MAX_ITERS = 8;
+constexpr int CC_TILE = 512;  // chunk partials per row staged in LDS by the weights kernel
+
+__device__ __forceinline__ bool cc_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+
+__device__ __forceinline__ unsigned int cc_bf16_bits(float r) {
+  const bf16 h = (bf16)r;
+  unsigned int hb = (unsigned int)__builtin_bit_cast(unsigned short, h);
+  if (r != r) hb = 0x7FC0u;
+  return hb;
+}
+
+// fp32 pattern of element j (0..7) of a vector of 8 bf16
+__device__ __forceinline__ unsigned int cc_elem(const u32x4& raw, int j) {
+  return (j & 1) ? (raw[j >> 1] & 0xFFFF0000u) : (raw[j >> 1] << 16);
+}
+
+// The trimmed kernel's rule on one element position (val: the rows' fp32 patterns): (sum of the kept) * inv.
+template <int PP>
+__device__ __forceinline__ float cc_trimmed(const unsigned int (&val)[PP], int f, int K, unsigned int live, float inv) {
+#pragma clang fp contract(off)
+  unsigned int key[PP], srt[PP];
+#pragma unroll
+  for (int k = 0; k < PP; ++k) {
+    const unsigned int neg = (unsigned int)((int)val[k] >> 31);
+    const unsigned int s = val[k] ^ ((neg & 0xFFFF0000u) | 0x80000000u);
+    const unsigned int dead = ((live >> k) & 1u) - 1u;
+    key[k] = s | (unsigned int)k | dead;
+    srt[k] = key[k];
+  }
+  tr_sort<PP>(srt);
+  unsigned int lo = 0u, hi = 0u;
+#pragma unroll
+  for (int k = 0; k < PP; ++k) {
+    if (k < PP / 2) lo |= srt[k] & (0u - (unsigned int)(k == f));
+    hi |= srt[k] & (0u - (unsigned int)(k == K - 1 - f));
+  }
+  float t = 0.f;
+#pragma unroll
+  for (int k = 0; k < PP; ++k) t += (key[k] >= lo && key[k] <= hi) ? __uint_as_float(val[k]) : 0.f;
+  return t * inv;
+}
+
+// The 256 thread sums s[k] of one chunk -> part[k * nchunks + c], for every live row k.
+template <int PP>
+__device__ __forceinline__ void cc_chunk_sum(float (&s)[PP], float (*wave_part)[PP], float* __restrict__ part,
+                                             int64_t nchunks, int64_t c, unsigned int live) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < PP; ++k) {
+    float a = s[k];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) a = a + __shfl_xor(a, o, 64);
+    if (lane == 0) wave_part[wid][k] = a;
+  }
+  __syncthreads();
+  if (threadIdx.x < PP && ((live >> threadIdx.x) & 1u)) {
+    const int k = threadIdx.x;
+    part[k * nchunks + c] = (wave_part[0][k] + wave_part[1][k]) + (wave_part[2][k] + wave_part[3][k]);
+  }
+  __syncthreads();  // wave_part is written again in the next chunk
+}
+
+// Init pass: v = float(median rule's result) and the chunk partials of the first distances.
+template <int PP>
+__global__ void __launch_bounds__(256) cclip_init_kernel(const bf16* __restrict__ in, float* __restrict__ v,
+                                                         float* __restrict__ part, int64_t n8, int64_t nchunks, int f,
+                                                         int K, unsigned int live, float inv) {
+#pragma clang fp contract(off)
+  __shared__ float wave_part[4][PP];
+  const int64_t n = n8 * 8;
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    float s[PP];
+#pragma unroll
+    for (int k = 0; k < PP; ++k) s[k] = 0.f;
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+      const int64_t i = c * CC_CHUNK_VEC + h * 256 + threadIdx.x;
+      if (i >= n8) continue;
+      const int64_t b = i * 8;
+      u32x4 raw[PP];
+#pragma unroll
+      for (int k = 0; k < PP; ++k) {
+        raw[k] = u32x4{0u, 0u, 0u, 0u};
+        if ((live >> k) & 1u) raw[k] = *(const u32x4*)(in + k * n + b);
+      }
+      float vv[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        unsigned int val[PP];
+#pragma unroll
+        for (int k = 0; k < PP; ++k) val[k] = cc_elem(raw[k], j);
+        const float r = cc_trimmed<PP>(val, f, K, live, inv);
+        const float c0 = __uint_as_float(cc_bf16_bits(r) << 16);  // the median rule's bf16 result, as fp32
+        vv[j] = c0;
+        const bool fin = cc_finite(c0);
+#pragma unroll
+        for (int k = 0; k < PP; ++k) {
+          const float e = fin ? __uint_as_float(val[k]) - c0 : 0.f;
+          if ((live >> k) & 1u) s[k] = s[k] + e * e;
+        }
+      }
+      *(f32x4*)(v + b) = f32x4{vv[0], vv[1], vv[2], vv[3]};
+      *(f32x4*)(v + b + 4) = f32x4{vv[4], vv[5], vv[6], vv[7]};
+    }
+    cc_chunk_sum<PP>(s, wave_part, part, nchunks, c, live);
+  }
+}
+
+// Weights: D_k = the row's chunk partials added in ascending order from +0, d = sqrt(D), tau, w. One workgroup: all
+// threads stage the partials through LDS (the next tile's loads are in flight while thread k adds row k's tile).
+template <int PP>
+__global__ void __launch_bounds__(256) cclip_weights_kernel(const float* __restrict__ part, int64_t nchunks, int P,
+                                                            int K, unsigned int live, float tau,
+                                                            float* __restrict__ w, float* __restrict__ w_user) {
+#pragma clang fp contract(off)
+  __shared__ float tile[PP][CC_TILE + 1];
+  __shared__ unsigned int dkey[PP];
+  const int tid = threadIdx.x;
+  float nxt[PP][CC_TILE / 256];
+  auto fetch = [&](int64_t base) {
+#pragma unroll
+    for (int k = 0; k < PP; ++k)
+#pragma unroll
+      for (int u = 0; u < CC_TILE / 256; ++u) {
+        const int64_t c = base + tid + 256 * u;
+        nxt[k][u] = (((live >> k) & 1u) && c < nchunks) ? part[k * nchunks + c] : 0.f;
+      }
+  };
+  fetch(0);
+  float D = 0.f;
+  for (int64_t base = 0; base < nchunks; base += CC_TILE) {
+#pragma unroll
+    for (int k = 0; k < PP; ++k)
+#pragma unroll
+      for (int u = 0; u < CC_TILE / 256; ++u) tile[k][tid + 256 * u] = nxt[k][u];
+    __syncthreads();
+    if (base + CC_TILE < nchunks) fetch(base + CC_TILE);
+    if (tid < PP) {
+      const int cnt = nchunks - base < CC_TILE ? (int)(nchunks - base) : CC_TILE;
+      for (int i = 0; i < cnt; ++i) D = D + tile[tid][i];
+    }
+    __syncthreads();
+  }
+  const bool alive = tid < PP && ((live >> tid) & 1u);
+  const bool fin = alive && cc_finite(D);
+  const float d = fin ? sqrtf(D) : 0.f;
+  // d >= +0: the fp32 patterns order like the values; a non-finite distance counts as +Inf, a dead row sorts behind
+  if (tid < PP) dkey[tid] = alive ? (fin ? __float_as_uint(d) : 0x7F800000u) : TR_DEAD_KEY;
+  __syncthreads();
+  if (tid < P) {
+    float t = tau;
+    if (!(tau > 0.f)) {
+      unsigned int srt[PP];
+#pragma unroll
+      for (int k = 0; k < PP; ++k) srt[k] = dkey[k];
+      tr_sort<PP>(srt);
+      unsigned int pick = 0u;
+#pragma unroll
+      for (int k = 0; k < PP / 2; ++k) pick |= srt[k] & (0u - (unsigned int)(k == (K - 1) / 2));  // (K-1)/2 < PP/2
+      t = __uint_as_float(pick);
+    }
+    const float wk = fin ? (d <= t ? 1.f : t / d) : 0.f;
+    w[tid] = wk;
+    if (w_user) w_user[tid] = wk;
+  }
+}
+
+// Step pass: v += (sum over the live rows with w > 0, ascending, of w (x - v)) * inv_K where v is finite. Not LAST:
+// v is written back and the next distances' chunk partials come from the rows still in registers. LAST: the bf16
+// result goes to every row of out and to mine.
+template <int PP, bool LAST>
+__global__ void __launch_bounds__(256) cclip_step_kernel(const bf16* in, bf16* out, bf16* mine, float* __restrict__ v,
+                                                         const float* __restrict__ w, float* __restrict__ part, int P,
+                                                         int64_t n8, int64_t nchunks, unsigned int live, float inv_k) {
+#pragma clang fp contract(off)
+  __shared__ float wave_part[4][PP];
+  const int64_t n = n8 * 8;
+  float wk[PP];
+  unsigned int use = 0u;  // live rows with a weight above zero: the others are skipped, never multiplied
+#pragma unroll
+  for (int k = 0; k < PP; ++k) {
+    wk[k] = (k < P && ((live >> k) & 1u)) ? w[k] : 0.f;
+    if (wk[k] > 0.f) use |= 1u << k;
+  }
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    float s[PP];
+#pragma unroll
+    for (int k = 0; k < PP; ++k) s[k] = 0.f;
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+      const int64_t i = c * CC_CHUNK_VEC + h * 256 + threadIdx.x;
+      if (i >= n8) continue;
+      const int64_t b = i * 8;
+      u32x4 raw[PP];  // all live rows of these 8 elements are read before anything is written (out may alias in)
+#pragma unroll
+      for (int k = 0; k < PP; ++k) {
+        raw[k] = u32x4{0u, 0u, 0u, 0u};
+        if ((live >> k) & 1u) raw[k] = *(const u32x4*)(in + k * n + b);
+      }
+      const f32x4 v0 = *(const f32x4*)(v + b), v1 = *(const f32x4*)(v + b + 4);
+      float vv[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+      u32x4 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float c0 = vv[j];
+        float x[PP];
+#pragma unroll
+        for (int k = 0; k < PP; ++k) x[k] = __uint_as_float(cc_elem(raw[k], j));
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < PP; ++k) {
+          const float term = wk[k] * (x[k] - c0);
+          t = ((use >> k) & 1u) ? t + term : t;
+        }
+        const float c1 = cc_finite(c0) ? c0 + t * inv_k : c0;
+        vv[j] = c1;
+        if (LAST) {
+          const unsigned int hb = cc_bf16_bits(c1);
+          if (j & 1)
+            o[j >> 1] |= hb << 16;
+          else
+            o[j >> 1] = hb;
+        } else {
+          const bool fin = cc_finite(c1);
+#pragma unroll
+          for (int k = 0; k < PP; ++k) {
+            const float e = fin ? x[k] - c1 : 0.f;
+            if ((live >> k) & 1u) s[k] = s[k] + e * e;
+          }
+        }
+      }
+      if (LAST) {
+        if (out)
+          for (int k = 0; k < P; ++k) *(u32x4*)(out + k * n + b) = o;
+        if (mine) *(u32x4*)(mine + b) = o;
+      } else {
+        *(f32x4*)(v + b) = f32x4{vv[0], vv[1], vv[2], vv[3]};
+        *(f32x4*)(v + b + 4) = f32x4{vv[4], vv[5], vv[6], vv[7]};
+      }
+    }
+    if (!LAST) cc_chunk_sum<PP>(s, wave_part, part, nchunks, c, live);
+  }
+}
+
+// One voter: its row, unchanged, to every row of out and to mine; its weight is 1.
+__global__ void __launch_bounds__(256) cclip_one_voter_kernel(const bf16* in, bf16* out, bf16* mine, int P, int64_t n8,
+                                                              int row, float* __restrict__ w_user) {
+  const int64_t n = n8 * 8;
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+    const u32x4 o = *(const u32x4*)(in + row * n + i * 8);
+    if (out)
+      for (int k = 0; k < P; ++k) *(u32x4*)(out + k * n + i * 8) = o;
+    if (mine) *(u32x4*)(mine + i * 8) = o;
+  }
+  if (w_user && blockIdx.x == 0 && threadIdx.x < P) w_user[threadIdx.x] = (int)threadIdx.x == row ? 1.f : 0.f;
+}
+
 }  // namespace vcx
 
 using namespace vcx;
@@ -170,4 +445,74 @@ void vcx_trimmed_reduce_bcast_bf16(const void* in, void* out, void* mine, int P,
   else
     VCX_TR_LAUNCH(16);
 #undef VCX_TR_LAUNCH
+}
+
+
+int vcx_cclip_max_workgroups() { return CC_MAX_BLOCKS; }
+
+int64_t vcx_cclip_workspace_floats(int P, int64_t n) {
+  const int64_t nchunks = (n / 8 + CC_CHUNK_VEC - 1) / CC_CHUNK_VEC;
+  return n + (int64_t)P * nchunks + TR_MAX_P;
+}
+
+// A call the kernels cannot take raises before anything is launched.
+void vcx_cclip_reduce_bcast_bf16(const void* in, void* out, void* mine, int P, int64_t n, uint32_t live_mask, float tau,
+                                 int iters, float* weights, float* workspace, hipStream_t s) {
+  const char* who = "cclip_reduce_bcast_bf16";
+  if (P < 1 || P > TR_MAX_P)
+    throw std::invalid_argument(std::string(who) + ": P must be in 1..16, got " + std::to_string(P));
+  if (live_mask == 0 || (P < 32 && (live_mask >> P) != 0))
+    throw std::invalid_argument(std::string(who) + ": live_mask must name at least one of the P rows and no other");
+  if (n < 0 || n % 8 != 0)
+    throw std::invalid_argument(std::string(who) + ": n must be a multiple of 8, got " + std::to_string(n));
+  if (!(tau >= 0.f) || tau > 3.402823466e38f)
+    throw std::invalid_argument(std::string(who) + ": tau must be finite and >= 0 (0: adaptive)");
+  if (iters < 1 || iters > CC_MAX_ITERS)
+    throw std::invalid_argument(std::string(who) + ": iters must be in 1..8, got " + std::to_string(iters));
+  if (!in || ((uintptr_t)in & 15) || ((uintptr_t)out & 15) || ((uintptr_t)mine & 15))
+    throw std::invalid_argument(std::string(who) + ": in, out and mine must be 16-byte aligned");
+  if (!workspace || ((uintptr_t)workspace & 15))
+    throw std::invalid_argument(std::string(who) + ": workspace must be 16-byte aligned");
+  if ((uintptr_t)weights & 3) throw std::invalid_argument(std::string(who) + ": weights must be 4-byte aligned");
+  if (n == 0) return;
+  const int K = __builtin_popcount(live_mask);
+  const int64_t n8 = n / 8;
+  if (K == 1) {
+    hipLaunchKernelGGL(cclip_one_voter_kernel, dim3(stream_grid(n8, 256)), dim3(256), 0, s, (const bf16*)in,
+                       (bf16*)out, (bf16*)mine, P, n8, __builtin_ctz(live_mask), weights);
+    return;
+  }
+  const int f = (K - 1) / 2;  // the median rule is the start
+  // the fp32 values of 1 / (K - 2f) and 1 / K as ops/robust.py forms them: the double quotient, rounded once more
+  const float inv = (float)(1.0 / (double)(K - 2 * f)), inv_k = (float)(1.0 / (double)K);
+  const int64_t nchunks = (n8 + CC_CHUNK_VEC - 1) / CC_CHUNK_VEC;
+  float* v = workspace;
+  float* part = v + n;
+  float* w = part + (int64_t)P * nchunks;
+  const dim3 grid((unsigned int)(nchunks < CC_MAX_BLOCKS ? nchunks : CC_MAX_BLOCKS)), block(256);
+#define VCX_CC_RUN(PP)                                                                                               \
+  do {                                                                                                               \
+    hipLaunchKernelGGL(cclip_init_kernel<PP>, grid, block, 0, s, (const bf16*)in, v, part, n8, nchunks, f, K,        \
+                       live_mask, inv);                                                                              \
+    for (int l = 0; l < iters; ++l) {                                                                                \
+      const bool last = l == iters - 1;                                                                              \
+      hipLaunchKernelGGL(cclip_weights_kernel<PP>, dim3(1), block, 0, s, part, nchunks, P, K, live_mask, tau, w,     \
+                         last ? weights : (float*)nullptr);                                                          \
+      if (last)                                                                                                      \
+        hipLaunchKernelGGL((cclip_step_kernel<PP, true>), grid, block, 0, s, (const bf16*)in, (bf16*)out,            \
+                           (bf16*)mine, v, w, part, P, n8, nchunks, live_mask, inv_k);                               \
+      else                                                                                                           \
+        hipLaunchKernelGGL((cclip_step_kernel<PP, false>), grid, block, 0, s, (const bf16*)in, (bf16*)out,           \
+                           (bf16*)mine, v, w, part, P, n8, nchunks, live_mask, inv_k);                               \
+    }                                                                                                                \
+  } while (0)
+  if (P <= 2)
+    VCX_CC_RUN(2);
+  else if (P <= 4)
+    VCX_CC_RUN(4);
+  else if (P <= 8)
+    VCX_CC_RUN(8);
+  else
+    VCX_CC_RUN(16);
+#undef VCX_CC_RUN
 }

@@ -63,6 +63,15 @@ void vcx_splitk_reduce(const void* part, void* acc, int S, int64_t n, int accumu
 // on anything else before a launch
 void vcx_trimmed_reduce_bcast_bf16(const void* in, void* out, void* mine, int P, int64_t n, int trim,
                                    uint32_t live_mask, float inv, int64_t* counts, hipStream_t s);
+// robust.hip: centered clipping of the live rows of in [P, n] (bf16) around the median rule's result, `iters`
+// (1..8) updates with clipping radius tau (finite, >= 0; 0: the (K-1)/2-th smallest distance of each update).
+// The bf16 result goes to every row of out (may alias in, or null) and to mine (or null), the last update's
+// weights to weights[P] (or null). workspace: vcx_cclip_workspace_floats(P, n) floats, 16-byte aligned, holds no
+// state between calls. 2 iters + 1 launches on s; throws std::invalid_argument before a launch
+void vcx_cclip_reduce_bcast_bf16(const void* in, void* out, void* mine, int P, int64_t n, uint32_t live_mask, float tau,
+                                 int iters, float* weights, float* workspace, hipStream_t s);
+int64_t vcx_cclip_workspace_floats(int P, int64_t n);
+int vcx_cclip_max_workgroups();  // workgroup cap of the passes: more chunks of 4096 elements are strided over
 
 // norm_act.hip
 void vcx_ln_fwd(const void* a, const void* b, void* xout, void* y, const void* w, const void* bias, float* mean,

@@ -12,7 +12,8 @@ resnet-tiny (synthetic ImageNet), llama3-8b / llama3.2-1b / llama-tiny (random t
 Trainers: localsgd (H local AdamW steps + averaging) | sharded (ZeRO-1 + buddy replicas).
 Compression: none | topk (ratio) | powersgd (rank) | q8 (8-bit blocks, nothing to tune).
 Aggregation (localsgd): mean | trimmed (--trim) | median: the coordinate-wise trimmed mean survives peers
-that stay alive and send wrong numbers (--byzantine: fault injection for exactly that).
+that stay alive and send wrong numbers (--byzantine: fault injection for exactly that); cclip
+(--clip-tau, --clip-iters): centered clipping bounds every peer's pull on a shard in the l2 norm.
 Optimizer state: fp32 | compact (fp8 m, fp16 v, one exponent per 32 elements; --opt-state).
 Checkpoints: utils/checkpoint.py format.
 """
@@ -137,10 +138,14 @@ def parse(argv=None):
                     help="fault injection: this peer stays alive and sends a wrong pseudo-gradient to every "
                          "averaging round (nan: all NaN, with --compression q8 NaN in every scale of its wire records; "
                          "flip: times -1, scale: times 1e4)")
-    ap.add_argument("--aggregate", default="mean", choices=["mean", "trimmed", "median"],
+    ap.add_argument("--aggregate", default="mean", choices=["mean", "trimmed", "median", "cclip"],
                     help="localsgd: how the peers' pseudo-gradients become one. trimmed / median: coordinate-wise "
-                         "trimmed mean, survives up to --trim wrong peers per coordinate")
+                         "trimmed mean, survives up to --trim wrong peers per coordinate. cclip: centered clipping, "
+                         "bounds every peer's pull on a shard's aggregate in the l2 norm")
     ap.add_argument("--trim", type=int, default=1, help="--aggregate trimmed: values dropped at each end")
+    ap.add_argument("--clip-tau", type=float, default=0.0,
+                    help="--aggregate cclip: clipping radius in the l2 norm of a shard (0: each update's median distance)")
+    ap.add_argument("--clip-iters", type=int, default=3, help="--aggregate cclip: updates per round, 1..8")
     ap.add_argument("--ckpt-dir", default=None)
     ap.add_argument("--ckpt-every", type=int, default=0)
     ap.add_argument("--resume", action="store_true")
@@ -155,6 +160,15 @@ def parse(argv=None):
         ap.error("--byzantine needs --trainer localsgd")
     if a.trim < 0:
         ap.error("--trim must be >= 0")
+    if not 1 <= a.clip_iters <= 8:
+        ap.error("--clip-iters must be in 1..8")
+    if not 0.0 <= a.clip_tau <= 3.4028234663852886e38:
+        ap.error("--clip-tau must be finite and >= 0 (0: adaptive)")
+    if a.aggregate == "cclip" and a.compression != "none":
+        ap.error(f"--aggregate cclip cannot be combined with --compression {a.compression}: the rule measures every "
+                 "peer's l2 distance on the uncompressed shard (over the q8 records it is not defined yet)")
+    if a.aggregate == "cclip" and a.algo not in (None, "direct"):
+        ap.error(f"--aggregate cclip runs over the 'direct' exchange only, got --algo {a.algo}")
     return a
 
 
@@ -211,7 +225,7 @@ def main(argv=None):
         cfg = LocalSGDConfig(lr=a.lr, H=a.H, algo=a.algo or "direct", outer_lr=a.outer_lr,
                              outer_momentum=a.outer_momentum, opt_state=a.opt_state,
                              comm_dtype=torch.bfloat16 if cuda else torch.float32,
-                             aggregate=a.aggregate, trim=a.trim,
+                             aggregate=a.aggregate, trim=a.trim, clip_tau=a.clip_tau, clip_iters=a.clip_iters,
                              robust_q8=a.compression == "q8" and a.aggregate != "mean")
         tr = LocalSGDTrainer(model, cfg, group=group, membership=membership, device=device)
         if a.compression == "q8" and a.byzantine == "nan":
@@ -297,6 +311,8 @@ def main(argv=None):
                 rec["trim_share"] = [round(s, 4) for s in tr.trim_share]  # per rank, of the round just done
                 if getattr(tr, "nonfinite_share", None) is not None:
                     rec["nonfinite_share"] = round(tr.nonfinite_share, 6)
+            if getattr(out, "synced", False) and getattr(tr, "clip_weight", None) is not None:
+                rec["clip_weight"] = [round(w, 4) for w in tr.clip_weight]  # per rank, of the round just done
             t_last = now
             print(json.dumps(rec), flush=True)
             if log:

@@ -10,4 +10,5 @@ from .norm import add_layernorm, add_rmsnorm, layernorm, rmsnorm  # noqa: F401
 from .rope import rope_qkv  # noqa: F401
 from .optim import (CompactState, adamw_flat_compact, adamw_step, adamw_step_compact, axpy_bf16,  # noqa: F401
                     check_compact_betas, f32_to_bf16, lsgd_apply, lsgd_delta, new_ostate, reduce_bcast_bf16)
-from .robust import trimmed_mean_reference, trimmed_reduce_bcast_bf16  # noqa: F401
+from .robust import (centered_clip_reference, cclip_reduce_bcast_bf16, trimmed_mean_reference,  # noqa: F401
+                     trimmed_reduce_bcast_bf16)

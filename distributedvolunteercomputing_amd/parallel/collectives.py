@@ -25,7 +25,8 @@ GPU buffers. All functions SUM in place; the caller applies the 1/P scale (fused
 local-SGD apply kernel).
 
 ``robust_mean_`` is the exception: it runs ``direct``'s exchange with a coordinate-wise trimmed
-mean (ops/robust.py) in the middle and leaves the MEAN in the buffer.
+mean (ops/robust.py) in the middle and leaves the MEAN in the buffer. ``cclip_mean_`` is the same
+exchange with centered clipping, the per-peer rule, in the middle.
 
 No reference analog: the reference has no collectives.
 """
@@ -254,3 +255,36 @@ def robust_mean_(t: torch.Tensor, group: PeerGroup, trim: int, live_ranks=None) 
     if buf is not t:
         t.copy_(buf[:n])
     return counts
+
+
+def cclip_mean_(t: torch.Tensor, group: PeerGroup, tau: float, iters: int, live_ranks=None) -> torch.Tensor:
+    """Centered clipping of `t` over the group, in place: ``robust_mean_``'s exchange (the same padding,
+    splits and two all-to-alls) with the per-peer rule of ops/robust.py as the middle step, so every shard
+    owner clips the peers' copies of its own shard around that shard's median. The all-zero padding has
+    centre 0 and adds nothing to any distance. `live_ranks`: the ranks that vote (default all).
+    Returns weights (fp32 [P], identical on every rank): per rank, the mean over the P shard owners of
+    its last-update weight. With no group or one peer the buffer is untouched and the weights are [1.0]."""
+    robust.check_clip(tau, iters)
+    if group is None or group.size == 1:
+        robust.mask_of(live_ranks, 1)
+        return torch.ones(1, dtype=torch.float32)
+    P, r = group.size, group.rank
+    mask = robust.mask_of(live_ranks, P)
+    robust.cclip_plan(P, mask, tau, iters)
+    n = t.numel()
+    L = _pad_len(n, P, 8 if t.dtype == torch.bfloat16 else 1)
+    buf = _padded(t, L)
+    m = L // P
+    split = [m] * P
+    weights = torch.zeros(P, dtype=torch.float32, device=buf.device)
+    recv = torch.empty_like(buf)  # [P, m]: row j = peer j's copy of MY shard
+    group.alltoall_(recv, buf, split, split)
+    mine = buf[r * m : (r + 1) * m]
+    ops.cclip_reduce_bcast_bf16(recv, recv, mine, P, tau, iters, mask, weights)  # recv reused as the send buffer
+    group.alltoall_(buf, recv, split, split)
+    weights = weights.to(group.device if group.backend == "nccl" else "cpu")
+    group.allreduce_(weights)
+    weights.div_(P)
+    if buf is not t:
+        t.copy_(buf[:n])
+    return weights

@@ -153,7 +153,8 @@ class FlatBuffers:
         its verdict is `commit`, so an aborted round leaves every peer's buffers as they were.
         aggregate "trimmed" / "median": the coordinate-wise trimmed mean of ops/robust.py over
         `live_ranks` (default all) instead: the vectors are all-gathered and every peer applies the
-        fp32 reference (a few hundred KB: no kernel needed)."""
+        fp32 reference (a few hundred KB: no kernel needed). aggregate "cclip" takes the median rule here:
+        the l2 norm of a vector that mixes means, variances and step counters means nothing."""
         if not self.entries or group is None or group.size == 1:
             return None
         v = self.as_fp32()
@@ -166,7 +167,7 @@ class FlatBuffers:
             mask = robust.mask_of(live_ranks, P)
             allv = torch.empty(P * v.numel(), dtype=torch.float32, device=v.device)
             group.all_gather_(allv, v)
-            trim = robust.effective_trim(aggregate, trim, bin(mask).count("1"))
+            trim = robust.effective_trim("median" if aggregate == "cclip" else aggregate, trim, bin(mask).count("1"))
             return robust.trimmed_mean_reference(allv.view(P, -1), trim, mask)[0]
         group.allreduce_(v)
         return v.div_(group.size)

@@ -14,6 +14,9 @@ mean over the same exchange (collectives.robust_mean_), which survives peers tha
 The robust rules combine with q8 compression (on request: LocalSGDConfig.robust_q8) and with no other: the
 q8 shard owner holds every peer's record of its shard before anything is summed, so its reduce kernel takes
 the trimmed mean of the decoded records instead (Quant8Compressor.allreduce_robust).
+``aggregate="cclip"`` is the per-peer rule over the same exchange (collectives.cclip_mean_): every shard owner
+clips the peers' copies of its shard around their median, so one peer moves a shard's aggregate by at most
+clip_iters * tau / K in l2 whatever it sends. It runs uncompressed, over `direct`, in this trainer only.
 
 Reference analog: the chunk (100 frames) is the reference's unit of independent work
 (worker.py:16, server.py:77-91); here the unit is H optimizer steps.
@@ -27,8 +30,8 @@ import torch
 
 from .. import ops
 from ..utils.trace import NULL_TRACER
-from ..ops.robust import AGGREGATES, effective_trim
-from .collectives import allreduce_sum_, robust_mean_
+from ..ops.robust import AGGREGATES, check_clip, effective_trim
+from .collectives import allreduce_sum_, cclip_mean_, robust_mean_
 from .compression import Quant8Compressor
 from .flat_params import FlatBuffers, FlatParams
 from .peer_group import PeerFailure
@@ -56,8 +59,12 @@ class LocalSGDConfig:
     # how the peers' pseudo-gradients become one: mean | trimmed | median. The robust rules
     # (ops/robust.py) drop the `trim` lowest and highest values of every coordinate (median: all but
     # the middle one or two), so up to `trim` peers per coordinate may send anything, NaN included
+    # cclip: centered clipping, the per-peer rule (clip_tau: the clipping radius in the l2 norm of a shard, 0 =
+    # each update's median distance; clip_iters: updates per round, 1..8)
     aggregate: str = "mean"
     trim: int = 1
+    clip_tau: float = 0.0
+    clip_iters: int = 3
     # let a robust rule run over the q8 exchange (Quant8Compressor.allreduce_robust). Off by default, so a robust
     # rule with any compressor is refused as before: over q8 the rule does not mean quite what it means on the
     # uncompressed pseudo-gradient (the aggregate is quantised again, and a coordinate whose aggregate is
@@ -66,14 +73,15 @@ class LocalSGDConfig:
     robust_q8: bool = False
 
     def __post_init__(self):
-        check_aggregate(self.aggregate, self.trim)
+        check_aggregate(self.aggregate, self.trim, self.clip_tau, self.clip_iters)
 
 
-def check_aggregate(aggregate, trim):
+def check_aggregate(aggregate, trim, clip_tau=0.0, clip_iters=3):
     if aggregate not in AGGREGATES:
         raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
     if not isinstance(trim, int) or trim < 0:
         raise ValueError(f"trim must be an integer >= 0, got {trim!r}")
+    check_clip(clip_tau, clip_iters)
 
 
 @dataclass
@@ -98,7 +106,8 @@ class LocalSGDTrainer:
         self.master = self.flat.param.float()
         if cfg.opt_state not in ("fp32", "compact"):
             raise ValueError(f"opt_state must be 'fp32' or 'compact', got {cfg.opt_state!r}")
-        check_aggregate(cfg.aggregate, cfg.trim)  # again: the config is mutable after its own check
+        # again: the config is mutable after its own check
+        check_aggregate(cfg.aggregate, cfg.trim, cfg.clip_tau, cfg.clip_iters)
         # fault injection (tests, `train --byzantine`): called on self.delta after lsgd_delta, before the collective
         self.delta_hook = None
         # the same for the wire: called on this peer's own q8 records (uint8 [P, record]) after encode
@@ -107,6 +116,9 @@ class LocalSGDTrainer:
         # robust rules over q8: the share of the coordinates whose aggregate was non-finite (more than `trim`
         # bad voters, or an overflowing sum) and came out as 0 in the last round
         self.nonfinite_share = None
+        # cclip: per rank, its weight in the last round's last update (the mean over the shard owners); 1 = never
+        # clipped, 0 = ignored. None under the other rules
+        self.clip_weight = None
         self._trim_clip_logged = False
         self.cstate = None  # compact mode: the moments live here and self.m / self.v are None
         if cfg.opt_state == "compact":
@@ -275,7 +287,12 @@ class LocalSGDTrainer:
         c = self.cfg
         robust = c.aggregate != "mean"
         if robust:
-            check_aggregate(c.aggregate, c.trim)
+            check_aggregate(c.aggregate, c.trim, c.clip_tau, c.clip_iters)
+            if c.aggregate == "cclip" and self.compressor is not None:
+                raise ValueError(f"aggregate='cclip' cannot be combined with the {type(self.compressor).__name__} "
+                                 "compressor: the rule measures every peer's l2 distance from the centre on the "
+                                 "uncompressed shard; top-k and PowerSGD never put the peers' own values on the "
+                                 "shard owner, and over the q8 records the rule is not defined yet")
             if self.compressor is not None and not isinstance(self.compressor, Quant8Compressor):
                 raise ValueError(f"aggregate={c.aggregate!r} cannot be combined with the "
                                  f"{type(self.compressor).__name__} compressor: a coordinate-wise rule needs every "
@@ -326,6 +343,17 @@ class LocalSGDTrainer:
         c = self.cfg
         live = self._voters(g, newcomers)
         K = g.size if live is None else len(live)
+        if c.aggregate == "cclip":
+            if self.time_reduce:
+                self._dev_sync()
+                t0 = time.perf_counter()
+            w = cclip_mean_(self.delta, g, c.clip_tau, c.clip_iters, live)
+            if self.time_reduce:
+                self._dev_sync()
+                self.reduce_log.append(((time.perf_counter() - t0) * 1e3,
+                                        self.delta.numel() * self.delta.element_size()))
+            self.clip_weight = w.tolist()
+            return self.delta, 1.0
         trim = effective_trim(c.aggregate, c.trim, K)
         if trim > (K - 1) // 2 and not self._trim_clip_logged:
             self._trim_clip_logged = True

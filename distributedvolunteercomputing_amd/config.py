@@ -38,6 +38,15 @@ class RuntimeConfig:
     # VCX_MLP_GRAD_FWD: the fused fc forward stores gelu'(pre) instead of pre, so the fc2 input gradient's
     # epilogue is one multiply (gemm_ps epilogues 5 / 6) instead of gelu'(pre) per element (4)
     mlp_grad_fwd: bool = True
+    # VCX_BWD_BATCH: GPT2.forward makes every W^T its backward reads in ONE transpose_bf16_many launch and hands each
+    # to its op (False: one transpose launch per layer inside the backward)
+    bwd_batch: bool = True
+    # VCX_FC_DGRAD_NT: with the batched W^T at hand, the fused MLP's fc input gradient is the NT library GEMM
+    # on fc_w^T (the fc2 forward's shape and kernel: 227.7 vs 251.3 us) instead of the NN one; needs bwd_batch
+    fc_dgrad_nt: bool = True
+    # VCX_LMHEAD_DGRAD_NT: wte^T joins the batched transposes and the LM head's input gradient is the NT library
+    # GEMM on it (GPT-2-small: 3.28 + 0.03 ms against 3.83 ms for the NN form); needs bwd_batch
+    lmhead_dgrad_nt: bool = True
     # VCX_GEMM_FWD: forward GEMMs x W^T (+ b) and input gradients dY W of the linear layers on "lib" or "vcx"
     # (csrc/kernels/gemm_f.hip, opt-in: 0.85-0.93x the library at the GPT-2 shapes, profiles/r6_gemm_f.txt)
     gemm_fwd: str = "lib"
@@ -120,6 +129,9 @@ _ENV = {
     "mlp": ("VCX_MLP", str),
     "dgrad_ps": ("VCX_DGRAD_PS", _bool),
     "mlp_grad_fwd": ("VCX_MLP_GRAD_FWD", _bool),
+    "bwd_batch": ("VCX_BWD_BATCH", _bool),
+    "fc_dgrad_nt": ("VCX_FC_DGRAD_NT", _bool),
+    "lmhead_dgrad_nt": ("VCX_LMHEAD_DGRAD_NT", _bool),
     "narrow_gemm": ("VCX_NARROW_GEMM", str),
     "resnet_conv1x1": ("VCX_RESNET_CONV1X1", str),
     "resnet_bn": ("VCX_RESNET_BN", str),

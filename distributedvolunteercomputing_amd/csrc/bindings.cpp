@@ -579,6 +579,40 @@ at::Tensor transpose_bf16(at::Tensor src, c10::optional<at::Tensor> dst) {
   return out;
 }
 
+// (transposes, launches): every srcs[i] transposed into dsts[i] (allocated when dsts is None) exactly as transpose_bf16
+// would, in one launch per JOB_TABLE_CAP matrices
+std::tuple<std::vector<at::Tensor>, int64_t> transpose_bf16_many(std::vector<at::Tensor> srcs,
+                                                                 c10::optional<std::vector<at::Tensor>> dsts) {
+  TORCH_CHECK(!dsts || dsts->size() == srcs.size(), "transpose_bf16_many: one dst per src");
+  std::vector<at::Tensor> outs;
+  std::vector<vcx::TransposeJob> jobs;
+  outs.reserve(srcs.size());
+  jobs.reserve(srcs.size());
+  for (size_t i = 0; i < srcs.size(); ++i) {
+    const at::Tensor& src = srcs[i];
+    TORCH_CHECK(src.is_cuda() && src.dim() == 2 && src.is_contiguous() && src.scalar_type() == at::kBFloat16 &&
+                    src.get_device() == srcs[0].get_device() && src.size(0) <= INT32_MAX && src.size(1) <= INT32_MAX,
+                "transpose_bf16_many: contiguous 2-D bf16 on one device");
+    at::Tensor out = dsts ? (*dsts)[i] : at::empty({src.size(1), src.size(0)}, src.options());
+    TORCH_CHECK(out.dim() == 2 && out.size(0) == src.size(1) && out.size(1) == src.size(0) && out.is_contiguous() &&
+                    out.scalar_type() == at::kBFloat16 && out.is_cuda() && out.get_device() == src.get_device(),
+                "transpose_bf16_many: dst");
+    vcx::TransposeJob j{};
+    j.src = src.data_ptr();
+    j.dst = out.data_ptr();
+    j.R = (int)src.size(0);
+    j.Cc = (int)src.size(1);
+    jobs.push_back(j);
+    outs.push_back(std::move(out));
+  }
+  int launches = 0;
+  if (!jobs.empty()) {
+    launches = vcx_transpose_bf16_many(jobs.data(), (int)jobs.size(), cur_stream());
+    TORCH_CHECK(launches >= 0, "transpose_bf16_many: a matrix of more than 2^31 tiles");
+  }
+  return {std::move(outs), (int64_t)launches};
+}
+
 // out (bf16) (+)= in (fp32); zero_in: in is zeroed after the read (a zero-at-rest accumulation buffer)
 void add_f32_into_bf16(at::Tensor in, at::Tensor out, bool accumulate, bool zero_in) {
   TORCH_CHECK(in.is_cuda() && in.scalar_type() == at::kFloat && out.scalar_type() == at::kBFloat16 &&
@@ -1130,6 +1164,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("gemm_nt", &gemm_nt, py::arg("a"), py::arg("b"), py::arg("c"), py::arg("c2") = py::none(),
         py::arg("bias") = py::none(), py::arg("colsum") = py::none(), py::arg("epi") = 0);
   m.def("transpose_bf16", &transpose_bf16, py::arg("src"), py::arg("dst") = py::none());
+  m.def("transpose_bf16_many", &transpose_bf16_many, py::arg("srcs"), py::arg("dsts") = py::none());
+  m.attr("JOB_TABLE_CAP") = (int64_t)vcx::JOBS_MAX;
   m.def("subsample_nhwc", &subsample_nhwc, py::arg("x"), py::arg("stride"));
   m.def("subsample_add_nhwc", &subsample_add_nhwc, py::arg("full"), py::arg("g"), py::arg("stride"));
   m.def("bcast_hw_nhwc", &bcast_hw_nhwc, py::arg("g"), py::arg("H"), py::arg("W"), py::arg("scale"));

@@ -30,6 +30,7 @@
 //     same 256-row A panel.
 #include <type_traits>
 
+#include "job_table.h"
 #include "lds_ring.h"
 
 namespace vcx {
@@ -309,11 +310,10 @@ __global__ void __launch_bounds__(NT, 1)
   }
 }
 
-// dst[r][c] = src[c][r] for a [R, Cc] bf16 matrix (weights: W -> W^T for the input-gradient GEMM)
-__global__ void __launch_bounds__(256) transpose_bf16_kernel(const bf16* __restrict__ src, bf16* __restrict__ dst,
-                                                             int R, int Cc) {
-  __shared__ bf16 t[64][65];
-  const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+// dst[r][c] = src[c][r] for a [R, Cc] bf16 matrix (weights: W -> W^T for the input-gradient GEMM): the 64 x 64
+// tile at (r0, c0) through the padded LDS tile t
+__device__ __forceinline__ void transpose_tile(const bf16* __restrict__ src, bf16* __restrict__ dst, int R, int Cc,
+                                               int r0, int c0, bf16 (*t)[65]) {
   for (int e = threadIdx.x; e < 64 * 64; e += 256) {
     const int rr = e >> 6, cc = e & 63;
     if (r0 + rr < R && c0 + cc < Cc) t[rr][cc] = src[(int64_t)(r0 + rr) * Cc + c0 + cc];
@@ -327,10 +327,9 @@ __global__ void __launch_bounds__(256) transpose_bf16_kernel(const bf16* __restr
 
 // the same with 16-B global loads and stores (R, Cc multiples of 8): each thread moves two 8-element
 // row pieces into a padded LDS tile, then gathers two 8-element column pieces of it
-__global__ void __launch_bounds__(256) transpose_bf16_v8_kernel(const bf16* __restrict__ src, bf16* __restrict__ dst,
-                                                                int R, int Cc) {
-  __shared__ __attribute__((aligned(16))) bf16 t[64][72];  // 144-B rows: 16-B aligned, reads spread over banks
-  const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
+// (t: 144-B rows: 16-B aligned, reads spread over banks)
+__device__ __forceinline__ void transpose_tile_v8(const bf16* __restrict__ src, bf16* __restrict__ dst, int R, int Cc,
+                                                  int r0, int c0, bf16 (*t)[72]) {
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int e = threadIdx.x + 256 * i, rr = e >> 3, cc = (e & 7) * 8;
@@ -347,6 +346,36 @@ __global__ void __launch_bounds__(256) transpose_bf16_v8_kernel(const bf16* __re
       *(bf16x8*)(dst + (int64_t)(c0 + cc) * R + r0 + rr) = v;
     }
   }
+}
+
+__global__ void __launch_bounds__(256) transpose_bf16_kernel(const bf16* __restrict__ src, bf16* __restrict__ dst,
+                                                             int R, int Cc) {
+  __shared__ bf16 t[64][65];
+  transpose_tile(src, dst, R, Cc, blockIdx.y * 64, blockIdx.x * 64, t);
+}
+
+__global__ void __launch_bounds__(256) transpose_bf16_v8_kernel(const bf16* __restrict__ src, bf16* __restrict__ dst,
+                                                                int R, int Cc) {
+  __shared__ __attribute__((aligned(16))) bf16 t[64][72];
+  transpose_tile_v8(src, dst, R, Cc, blockIdx.y * 64, blockIdx.x * 64, t);
+}
+
+// Every tile of every job of the table in one launch (job_table.h): workgroup b runs one 64 x 64 tile of the
+// job it falls in, with the body vcx_transpose_bf16 would pick for that matrix. The branch is uniform per
+// workgroup, so each body's barrier is reached by all of its threads.
+__global__ void __launch_bounds__(256) transpose_bf16_many_kernel(const TransposeTable tab) {
+  __shared__ __attribute__((aligned(16))) bf16 t[64 * 72];  // the larger of the two tiles (the scalar one: 64 x 65)
+  const int b = blockIdx.x;
+  const int j = job_of_workgroup(tab.first, tab.njobs, b);
+  const int tile = b - tab.first[j], tx = tab.job[j].tiles_x;
+  const int r0 = (tile / tx) * 64, c0 = (tile % tx) * 64;
+  const bf16* src = (const bf16*)tab.job[j].src;
+  bf16* dst = (bf16*)tab.job[j].dst;
+  const int R = tab.job[j].R, Cc = tab.job[j].Cc;
+  if (tab.job[j].v8)
+    transpose_tile_v8(src, dst, R, Cc, r0, c0, (bf16(*)[72])t);
+  else
+    transpose_tile(src, dst, R, Cc, r0, c0, (bf16(*)[65])t);
 }
 
 // out_bf16[i] += (bf16) in_f32[i] (the epilogue's fp32 column sums into a flat .grad slot); zero_in: in[i] = 0
@@ -410,6 +439,19 @@ void vcx_transpose_bf16(const void* src, void* dst, int R, int Cc, hipStream_t s
   }
   hipLaunchKernelGGL(gemm::transpose_bf16_kernel, dim3((Cc + 63) / 64, (R + 63) / 64), dim3(256), 0, s,
                      (const bf16*)src, (bf16*)dst, R, Cc);
+}
+
+int vcx_transpose_bf16_many(const vcx::TransposeJob* jobs, int n, hipStream_t s) {
+  int launches = 0;
+  for (int i = 0; i < n;) {
+    TransposeTable tab{};
+    i = pack_transpose_jobs(jobs, n, i, &tab);
+    if (i < 0) return -1;
+    if (tab.njobs == 0) break;  // only empty matrices were left
+    hipLaunchKernelGGL(gemm::transpose_bf16_many_kernel, dim3(tab.first[tab.njobs]), dim3(256), 0, s, tab);
+    ++launches;
+  }
+  return launches;
 }
 
 void vcx_add_f32_into_bf16(float* in, void* out, int n, int accumulate, int zero_in, hipStream_t s) {

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "job_table.h"
+
 // optim.hip
 void vcx_grad_sumsq(const void* g, int64_t n, float* ostate, hipStream_t s);
 void vcx_adam_prologue(float* ostate, float max_norm, hipStream_t s);
@@ -53,6 +55,9 @@ int vcx_gemm_ps_grid(int M, int N, int grid_cap);
 void vcx_gemm_ps(const void* A, const void* B, void* C, void* C2, const void* bias, float* colsum, int M, int N,
                  int K, int lda, int ldb, int ldc, int epi, int grid_cap, hipStream_t s);
 void vcx_transpose_bf16(const void* src, void* dst, int R, int Cc, hipStream_t s);
+// every matrix of jobs[0..n) transposed as vcx_transpose_bf16 would, in one launch per JOBS_MAX jobs (job_table.h:
+// the table travels by value as the kernel argument); returns the launches made, -1 for a matrix too large
+int vcx_transpose_bf16_many(const vcx::TransposeJob* jobs, int n, hipStream_t s);
 void vcx_add_f32_into_bf16(float* in, void* out, int n, int accumulate, int zero_in, hipStream_t s);
 void vcx_reduce_bcast_bf16(const void* in, void* out, void* mine, int P, int64_t n, hipStream_t s);
 void vcx_splitk_reduce(const void* part, void* acc, int S, int64_t n, int accumulate, hipStream_t s);

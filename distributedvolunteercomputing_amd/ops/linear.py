@@ -95,6 +95,37 @@ def gemm_f(a, w, bias=None):
 def transpose_weight(w):
     """W^T as a contiguous bf16 matrix (HIP transpose; weights only — a few MB)."""
     return native().transpose_bf16(w.contiguous())
+
+
+def transpose_weights(ws, out=None):
+    """[W^T for W in ws] (2-D bf16) in one HIP launch per ``native().JOB_TABLE_CAP`` matrices, bit-identical to
+    ``transpose_weight``. ``out``: the list a previous call returned for the same weights (persistent buffers, one
+    per weight), written again in place; anything else allocates. The handles are valid for the forward that made
+    them and that forward's backward only: the flat AdamW kernel rewrites the weights without a version bump, so the
+    caller makes them anew every forward and hands them to the ops (``linear(..., wt=)``, ``mlp_gelu(..., w1t=,
+    w2t=)``) instead of caching them."""
+    ws = [w.contiguous() for w in ws]
+    if out is not None and not (len(out) == len(ws) and all(
+            o.shape == (w.shape[1], w.shape[0]) and o.device == w.device and o.dtype == w.dtype for o, w in zip(out, ws))):
+        out = None
+    return native().transpose_bf16_many(ws, out)[0]
+
+
+def linear_wants_wt(M: int, w, t) -> bool:
+    """True when the backward of ``linear(x[M, K], w)`` reads W^T (``t``: the activations)."""
+    N, K = _w2(w).shape
+    return (gemm_nt_ok(M, K, N, t) or gemm_f_ok(M, K, N, t) or narrow_gemm_ok(M, K, N, t) or dgrad_ps_ok(M, K, N, t))
+
+
+def mlp_wants_wt(x, w1, w2):
+    """(fc, fc2): which of W1^T, W2^T the backward of ``mlp_gelu(x, w1, b1, w2)`` reads."""
+    mode = _mlp_mode(x, w1, w2)
+    if mode is None:
+        M = x.numel() // x.shape[-1]
+        return linear_wants_wt(M, w1, x), linear_wants_wt(M, w2, x)
+    return mode == "nt" or bool(config.get().fc_dgrad_nt), True
+
+
 _CHOICE: dict = {}  # (shapes, layout, bias) -> "torch" | "lt"
 
 
@@ -377,7 +408,7 @@ def subsample_tap(x: torch.Tensor, join: GradJoin, stride: int) -> torch.Tensor:
 
 class _Linear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b, bias_grad_elsewhere=False, join=None, deposit=False):
+    def forward(ctx, x, w, b, bias_grad_elsewhere=False, join=None, deposit=False, wt=None):
         # w: [N, K], or a 1x1 convolution's [N, K, 1, 1] weight itself (not a view of it: its gradient
         # then goes straight into the parameter's flat .grad, no view-backward + accumulation pass)
         ctx.save_for_backward(x, w)
@@ -386,6 +417,7 @@ class _Linear(torch.autograd.Function):
         ctx.has_bias = b is not None and not bias_grad_elsewhere
         ctx.bias = b
         ctx.join, ctx.deposit = join, deposit
+        ctx.wt = wt  # W^T made by this forward's transpose_weights (kept for a second backward pass)
         if deposit:
             join.pending, join.ran = None, False
         x2 = x.reshape(-1, x.shape[-1])
@@ -420,18 +452,24 @@ class _Linear(torch.autograd.Function):
         elif base is not None:
             dx = (mm(dy2, w) + base).view(x.shape) if ctx.needs_input_grad[0] else None
         elif ctx.needs_input_grad[0]:
+            wt = ctx.wt
             if gemm_nt_ok(dy2.shape[0], K, N, dy2):
-                dx = gemm_nt(dy2, transpose_weight(w)).view(x.shape)
+                dx = gemm_nt(dy2, transpose_weight(w) if wt is None else wt).view(x.shape)
             elif gemm_f_ok(dy2.shape[0], K, N, dy2):
-                dx = gemm_f(dy2, transpose_weight(w)).view(x.shape)
+                dx = gemm_f(dy2, transpose_weight(w) if wt is None else wt).view(x.shape)
             elif narrow_gemm_ok(dy2.shape[0], K, N, dy2):
-                dx = narrow_gemm(dy2, transpose_weight(w)).view(x.shape)
+                dx = narrow_gemm(dy2, transpose_weight(w) if wt is None else wt).view(x.shape)
             elif dgrad_ps_ok(dy2.shape[0], K, N, dy2):
                 # dX = dY W on the persistent hand-written GEMM (B = W^T, a few MB): faster than the
                 # library at the GPT-2 attention shapes (profiles/r4_gemm_ps_bench.txt: dg_qkv, dg_proj)
                 dx = torch.empty(dy2.shape[0], K, device=dy2.device, dtype=dy2.dtype)
-                native().gemm_ps(dy2, transpose_weight(w), dx)
+                native().gemm_ps(dy2, transpose_weight(w) if wt is None else wt, dx)
                 dx = dx.view(x.shape)
+            elif wt is not None:
+                # a handle and no hand-written kernel for the shape: dX = dY (W^T)^T as the NT library GEMM (the
+                # GPT-2-small LM head: 3.28 ms + 0.03 ms for wte^T against 3.83 ms for the NN form,
+                # profiles/bwd_helpers_step_kernels.txt); the caller decides by giving the handle
+                dx = mm(dy2, wt, trans_b=True).view(x.shape)
             else:
                 dx = mm(dy2, w).view(x.shape)
         if deposit and dx is not None and not depo.ran and dx.is_contiguous():
@@ -453,9 +491,9 @@ class _Linear(torch.autograd.Function):
             dy2.record_stream(side)  # keep the inputs' memory until the side stream is done with it
             x2.record_stream(side)
             _queue_join(main, side, dy2.device)
-            return dx, None, None, None, None, None
+            return dx, None, None, None, None, None, None
         dw, db = _param_grads(dy2, x2, w, bias, want_w, want_b)
-        return dx, dw, db, None, None, None
+        return dx, dw, db, None, None, None, None
 
 
 def native_linear_ok(w: torch.Tensor) -> bool:
@@ -464,14 +502,16 @@ def native_linear_ok(w: torch.Tensor) -> bool:
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = None,
-           bias_grad_elsewhere: bool = False, join: GradJoin | None = None, deposit: bool = False) -> torch.Tensor:
+           bias_grad_elsewhere: bool = False, join: GradJoin | None = None, deposit: bool = False,
+           wt: torch.Tensor | None = None) -> torch.Tensor:
     """y = x @ w^T (+ b), x [..., K], w [N, K] (or a 1x1 convolution's [N, K, 1, 1]). With
     bias_grad_elsewhere the backward leaves the bias gradient to y's consumer (e.g.
     ``causal_attention(qkv, bias=b)``), which must then be y's only consumer and return
     d(loss)/d(b) = column sums of dy for the same tensor. ``join``: see GradJoin (deposit = this
-    layer's backward leaves its input gradient in the join for a later consumer)."""
+    layer's backward leaves its input gradient in the join for a later consumer). ``wt``: w^T from this forward's
+    ``transpose_weights`` (the backward then makes none of its own)."""
     if native_linear_ok(w):
-        return _Linear.apply(x, w, b, bias_grad_elsewhere, join, deposit)
+        return _Linear.apply(x, w, b, bias_grad_elsewhere, join, deposit, wt)
     assert join is None, "a GradJoin needs the native linear path (its backward consumes the joined gradient)"
     return F.linear(x, _w2(w), b)
 
@@ -500,7 +540,7 @@ class _MlpGelu(torch.autograd.Function):
     four run the tiled gemm_nt (VCX_GEMM=vcx)."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, ps):
+    def forward(ctx, x, w1, b1, w2, ps, w1t=None, w2t=None):
         C = native()
         x2 = x.reshape(-1, x.shape[-1])
         M, F_ = x2.shape[0], w1.shape[0]
@@ -517,6 +557,7 @@ class _MlpGelu(torch.autograd.Function):
         ctx.save_for_backward(x2, w1, b1, w2, pre, act)
         ctx.xshape = x.shape
         ctx.ps = ps
+        ctx.w1t, ctx.w2t = w1t, w2t  # from this forward's transpose_weights (kept for a second backward pass)
         ctx.grad_fwd = bool(ps and config.get().mlp_grad_fwd)
         return y.view(*x.shape[:-1], w2.shape[0])
 
@@ -531,10 +572,12 @@ class _MlpGelu(torch.autograd.Function):
         # the flat .grad zeroes again (no fill launch per layer), a fresh zero tensor when the sums are returned
         cs = _colsum_buffer(F_, dy.device) if gb is not None else torch.zeros(F_, device=dy.device, dtype=torch.float32)
         dpre = torch.empty_like(pre)
+        w1t = ctx.w1t
+        w2t = transpose_weight(w2) if ctx.w2t is None else ctx.w2t
         if ctx.ps:
-            C.gemm_ps(dy2, transpose_weight(w2), dpre, pre, None, cs, 6 if ctx.grad_fwd else 4)
+            C.gemm_ps(dy2, w2t, dpre, pre, None, cs, 6 if ctx.grad_fwd else 4)
         else:
-            C.gemm_nt(dy2, transpose_weight(w2), dpre, pre, None, cs, 3)
+            C.gemm_nt(dy2, w2t, dpre, pre, None, cs, 3)
         dw2, _ = _param_grads(dy2, act, w2, None, ctx.needs_input_grad[3], False)
         dw1, _ = _param_grads(dpre, x2, w1, None, ctx.needs_input_grad[1], False)
         db1 = None
@@ -545,8 +588,16 @@ class _MlpGelu(torch.autograd.Function):
                 db1 = cs.to(b1.dtype)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = (mm(dpre, w1) if ctx.ps else gemm_nt(dpre, transpose_weight(w1))).view(ctx.xshape)
-        return dx, dw1, db1, dw2, None
+            if not ctx.ps:
+                dx = gemm_nt(dpre, transpose_weight(w1) if w1t is None else w1t)
+            elif w1t is not None and config.get().fc_dgrad_nt:
+                # dX = dpre (W1^T)^T as the NT library GEMM: the fc2 forward's shape and kernel, 227.7 vs 251.3 us for
+                # the NN form at the GPT-2-small step (profiles/bwd_helpers_step_kernels.txt)
+                dx = mm(dpre, w1t, trans_b=True)
+            else:
+                dx = mm(dpre, w1)
+            dx = dx.view(ctx.xshape)
+        return dx, dw1, db1, dw2, None, None, None
 
 
 _COLSUM = {}
@@ -580,12 +631,12 @@ def _mlp_mode(x, w1, w2):
     return None
 
 
-def mlp_gelu(x, w1, b1, w2):
+def mlp_gelu(x, w1, b1, w2, w1t=None, w2t=None):
     """gelu_tanh(x W1^T + b1) W2^T (GPT-2 MLP without the fc2 bias, which the following fused
-    add + LayerNorm applies)."""
+    add + LayerNorm applies). ``w1t`` / ``w2t``: W1^T / W2^T from this forward's ``transpose_weights``."""
     mode = _mlp_mode(x, w1, w2)
     if mode is not None:
-        return _MlpGelu.apply(x, w1, b1, w2, mode == "ps")
+        return _MlpGelu.apply(x, w1, b1, w2, mode == "ps", w1t, w2t)
     from .activations import bias_gelu
 
-    return linear(bias_gelu(linear(x, w1), b1), w2)
+    return linear(bias_gelu(linear(x, w1, wt=w1t), b1), w2, wt=w2t)

@@ -127,10 +127,11 @@ class _LMHeadXEnt(torch.autograd.Function):
         return dx, dw, None, None, None, None
 
 
-def lm_head_cross_entropy(x, w, targets, vocab: int, chunk: int | None = None):
+def lm_head_cross_entropy(x, w, targets, vocab: int, chunk: int | None = None, wt=None):
     """Mean cross-entropy of logits = x @ w^T over the first `vocab` columns (w [Vp, K] may be
     padded). On the GPU with `chunk` rows (default: config ``lmhead_chunk``) per GEMM + xent pass;
-    chunk 0 (or CPU tensors) = the unchunked ``cross_entropy(linear(x, w))``."""
+    chunk 0 (or CPU tensors) = the unchunked ``cross_entropy(linear(x, w))``, which hands ``wt`` (w^T from this
+    forward's ``transpose_weights``) to the linear layer."""
     from .linear import linear
 
     x2 = x.reshape(-1, x.shape[-1])
@@ -142,5 +143,5 @@ def lm_head_cross_entropy(x, w, targets, vocab: int, chunk: int | None = None):
         t = t.contiguous().long()
         nvalid = (t >= 0).sum().clamp_min(1).to(torch.float32).reshape(1)
         return _LMHeadXEnt.apply(x2.contiguous(), w, t, vocab, nvalid, mc)
-    return cross_entropy(linear(x2, w), t, vocab=vocab)
+    return cross_entropy(linear(x2, w, wt=wt), t, vocab=vocab)
 

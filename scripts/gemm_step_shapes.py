@@ -32,8 +32,11 @@ for name, (N, K) in shapes.items():
     fl = 2.0 * M * N * K
     cases.append((f"fwd   {name}", fl, lambda x=x, w=w: F.linear(x, w)))
     cases.append((f"dgrad {name}", fl, lambda dy=dy, w=w: torch.mm(dy, w)))
+    wt = L.transpose_weight(w)
+    # dX = dY (W^T)^T: the NT library GEMM on the transposed weight (ops/linear.py fc_dgrad_nt), and what W^T costs
+    cases.append((f"dgrad {name} NT on W^T", fl, lambda dy=dy, wt=wt: F.linear(dy, wt)))
+    cases.append((f"transpose {name}", 0.0, lambda w=w, wt=wt: C.transpose_bf16(w, wt)))
     if C.gemm_ps_supported(M, K, N, 0):  # dX[M, K] = dY W on W^T (ops/linear.py dgrad_ps_ok)
-        wt = L.transpose_weight(w)
         dx = torch.empty(M, K, device=dev, dtype=torch.bfloat16)
         cases.append((f"dgrad {name} gemm_ps", fl, lambda dy=dy, wt=wt, dx=dx: C.gemm_ps(dy, wt, dx)))
     cases.append((f"wgrad {name} default", fl, lambda dy=dy, x=x, gw=gw: L.wgrad(dy, x, out=gw, accumulate=True)))
@@ -69,4 +72,4 @@ for rnd in range(5):
 print(f"tuned_gemms={TUNED}  M={M}", flush=True)
 for name, fl, _ in cases:
     t = sorted(res[name])[len(res[name]) // 2]
-    print(f"{name:34s} {t:9.1f} us  {fl / t / 1e6:7.0f} TF", flush=True)
+    print(f"{name:34s} {t:9.1f} us" + (f"  {fl / t / 1e6:7.0f} TF" if fl else ""), flush=True)  # fl == 0: no GEMM

@@ -631,32 +631,39 @@ void reduce_bcast_bf16(at::Tensor in, c10::optional<at::Tensor> out, c10::option
                        "reduce_bcast: out must match in");
   if (mine) TORCH_CHECK(mine->numel() == n && mine->is_contiguous() && mine->scalar_type() == at::kBFloat16,
                         "reduce_bcast: mine must hold n bf16");
-  vcx_reduce_bcast_bf16(in.data_ptr(), out ? out->data_ptr() : nullptr, mine ? mine->data_ptr() : nullptr, (int)P, n,
-                        cur_stream());
+  vcx_reduce_bcast_bf16(in.data_ptr(), opt_ptr(out), opt_ptr(mine), (int)P, n, cur_stream());
+}
+
+// What the robust middle steps of the direct all-reduce (robust.hip) share: in [P, n] bf16, the live rows, and the
+// optional out [P, n] and mine [n]. Returns n. `who` is the op's name in the messages.
+int64_t check_robust_rows(const char* who, const at::Tensor& in, int64_t P, int64_t live_mask,
+                          const c10::optional<at::Tensor>& out, const c10::optional<at::Tensor>& mine) {
+  TORCH_CHECK(in.is_cuda() && in.scalar_type() == at::kBFloat16 && in.is_contiguous(), who,
+              ": in must be a contiguous bf16 GPU tensor");
+  TORCH_CHECK(P >= 1 && P <= 16, who, ": P must be in 1..16, got ", P);
+  TORCH_CHECK(live_mask > 0 && (live_mask >> P) == 0, who,
+              ": live_mask must name at least one of the P rows and no other, got ", live_mask);
+  const int64_t n = in.numel() / P;
+  TORCH_CHECK(n * P == in.numel() && n % 8 == 0, who, ": numel must be P * n with n % 8 == 0");
+  auto aligned = [](const at::Tensor& t, uintptr_t a) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % a == 0; };
+  TORCH_CHECK(aligned(in, 16), who, ": in must be 16-byte aligned");
+  if (out)
+    TORCH_CHECK(out->is_cuda() && out->get_device() == in.get_device() && out->numel() == in.numel() &&
+                    out->is_contiguous() && out->scalar_type() == at::kBFloat16 && aligned(*out, 16),
+                who, ": out must match in (bf16, same length, 16-byte aligned)");
+  if (mine)
+    TORCH_CHECK(mine->is_cuda() && mine->get_device() == in.get_device() && mine->numel() == n &&
+                    mine->is_contiguous() && mine->scalar_type() == at::kBFloat16 && aligned(*mine, 16),
+                who, ": mine must hold n bf16, 16-byte aligned");
+  return n;
 }
 
 // Robust middle step of the direct all-reduce (robust.hip). Everything is checked here, before the launcher's
 // own checks, so a refused call leaves out, mine and counts unwritten.
 void trimmed_reduce_bcast_bf16(at::Tensor in, c10::optional<at::Tensor> out, c10::optional<at::Tensor> mine, int64_t P,
                                int64_t trim, int64_t live_mask, double inv, c10::optional<at::Tensor> counts) {
-  TORCH_CHECK(in.is_cuda() && in.scalar_type() == at::kBFloat16 && in.is_contiguous(),
-              "trimmed_reduce_bcast: in must be a contiguous bf16 GPU tensor");
-  TORCH_CHECK(P >= 1 && P <= 16, "trimmed_reduce_bcast: P must be in 1..16, got ", P);
-  TORCH_CHECK(live_mask > 0 && (live_mask >> P) == 0,
-              "trimmed_reduce_bcast: live_mask must name at least one of the P rows and no other, got ", live_mask);
+  const int64_t n = check_robust_rows("trimmed_reduce_bcast", in, P, live_mask, out, mine);
   TORCH_CHECK(trim >= 0, "trimmed_reduce_bcast: trim must be >= 0");
-  const int64_t n = in.numel() / P;
-  TORCH_CHECK(n * P == in.numel() && n % 8 == 0, "trimmed_reduce_bcast: numel must be P * n with n % 8 == 0");
-  auto aligned = [](const at::Tensor& t, uintptr_t a) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % a == 0; };
-  TORCH_CHECK(aligned(in, 16), "trimmed_reduce_bcast: in must be 16-byte aligned");
-  if (out)
-    TORCH_CHECK(out->is_cuda() && out->get_device() == in.get_device() && out->numel() == in.numel() &&
-                    out->is_contiguous() && out->scalar_type() == at::kBFloat16 && aligned(*out, 16),
-                "trimmed_reduce_bcast: out must match in (bf16, same length, 16-byte aligned)");
-  if (mine)
-    TORCH_CHECK(mine->is_cuda() && mine->get_device() == in.get_device() && mine->numel() == n &&
-                    mine->is_contiguous() && mine->scalar_type() == at::kBFloat16 && aligned(*mine, 16),
-                "trimmed_reduce_bcast: mine must hold n bf16, 16-byte aligned");
   if (counts)
     TORCH_CHECK(counts->is_cuda() && counts->get_device() == in.get_device() && counts->numel() == P &&
                     counts->is_contiguous() && counts->scalar_type() == at::kLong,
@@ -670,26 +677,10 @@ void trimmed_reduce_bcast_bf16(at::Tensor in, c10::optional<at::Tensor> out, c10
 // weights; the workspace (the fp32 centre, the distances' chunk partials, the weights) is allocated here.
 void cclip_reduce_bcast_bf16(at::Tensor in, c10::optional<at::Tensor> out, c10::optional<at::Tensor> mine, int64_t P,
                              int64_t live_mask, double tau, int64_t iters, c10::optional<at::Tensor> weights) {
-  TORCH_CHECK(in.is_cuda() && in.scalar_type() == at::kBFloat16 && in.is_contiguous(),
-              "cclip_reduce_bcast: in must be a contiguous bf16 GPU tensor");
-  TORCH_CHECK(P >= 1 && P <= 16, "cclip_reduce_bcast: P must be in 1..16, got ", P);
-  TORCH_CHECK(live_mask > 0 && (live_mask >> P) == 0,
-              "cclip_reduce_bcast: live_mask must name at least one of the P rows and no other, got ", live_mask);
+  const int64_t n = check_robust_rows("cclip_reduce_bcast", in, P, live_mask, out, mine);
   TORCH_CHECK(tau >= 0.0 && tau <= 3.4028234663852886e38,  // a finite fp32 value; a NaN fails both comparisons
               "cclip_reduce_bcast: tau must be finite and >= 0 (0: adaptive), got ", tau);
   TORCH_CHECK(iters >= 1 && iters <= 8, "cclip_reduce_bcast: iters must be in 1..8, got ", iters);
-  const int64_t n = in.numel() / P;
-  TORCH_CHECK(n * P == in.numel() && n % 8 == 0, "cclip_reduce_bcast: numel must be P * n with n % 8 == 0");
-  auto aligned = [](const at::Tensor& t, uintptr_t a) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % a == 0; };
-  TORCH_CHECK(aligned(in, 16), "cclip_reduce_bcast: in must be 16-byte aligned");
-  if (out)
-    TORCH_CHECK(out->is_cuda() && out->get_device() == in.get_device() && out->numel() == in.numel() &&
-                    out->is_contiguous() && out->scalar_type() == at::kBFloat16 && aligned(*out, 16),
-                "cclip_reduce_bcast: out must match in (bf16, same length, 16-byte aligned)");
-  if (mine)
-    TORCH_CHECK(mine->is_cuda() && mine->get_device() == in.get_device() && mine->numel() == n &&
-                    mine->is_contiguous() && mine->scalar_type() == at::kBFloat16 && aligned(*mine, 16),
-                "cclip_reduce_bcast: mine must hold n bf16, 16-byte aligned");
   if (weights)
     TORCH_CHECK(weights->is_cuda() && weights->get_device() == in.get_device() && weights->numel() == P &&
                     weights->is_contiguous() && weights->scalar_type() == at::kFloat,

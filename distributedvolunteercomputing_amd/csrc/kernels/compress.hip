@@ -23,10 +23,7 @@
 // streaming kernels (encode, reduce on the shard owner, decode), described at their section below,
 // and the robust reduce (the trimmed mean of ops/robust.py over the decoded records) that takes the
 // place of the rank-order sum under --aggregate trimmed | median.
-#include "vcx_common.h"
-
-#include <stdexcept>
-#include <string>
+#include "robust_common.h"
 
 namespace vcx {
 
@@ -1130,9 +1127,7 @@ void vcx_q8_reduce(const uint8_t* recv, int P, int64_t m, float avg_scale, uint8
 void vcx_q8_trimmed_reduce(const uint8_t* recv, int P, int64_t m, int trim, uint32_t live_mask, int64_t valid,
                            uint8_t* out_record, int64_t* counts, int64_t* nonfinite, hipStream_t s) {
   const std::string who = "q8_trimmed_reduce";
-  if (P < 1 || P > 16) throw std::invalid_argument(who + ": P must be in 1..16, got " + std::to_string(P));
-  if (live_mask == 0 || (live_mask >> P) != 0)
-    throw std::invalid_argument(who + ": live_mask must name at least one of the P rows and no other");
+  check_rows(who, P, live_mask);
   if (m <= 0 || m % Q8_BLOCK != 0 || m >= INT32_MAX)
     throw std::invalid_argument(who + ": m must be a positive multiple of 128 below 2^31, got " + std::to_string(m));
   if (valid < 0 || valid > m)
@@ -1143,23 +1138,14 @@ void vcx_q8_trimmed_reduce(const uint8_t* recv, int P, int64_t m, int trim, uint
     throw std::invalid_argument(who + ": out_record must be 4-byte aligned");
   if (((uintptr_t)counts | (uintptr_t)nonfinite) & 7)
     throw std::invalid_argument(who + ": counts and nonfinite must be 8-byte aligned");
-  const int K = __builtin_popcount(live_mask);
-  const int f = trim < (K - 1) / 2 ? trim : (K - 1) / 2;
-  const float inv = (float)(1.0 / (double)(K - 2 * f));  // the fp32 value ops/robust.py trim_plan computes
+  const int K = __builtin_popcount(live_mask), f = trim_of(trim, K);
+  const float inv = trim_inv(K, f);
   const uint32_t bps = (uint32_t)(m / Q8_BLOCK);
   const dim3 grid(stream_grid(m / 8, 256, Q8_TRIMMED_MAX_BLOCKS)), block(256);
-#define VCX_Q8T_LAUNCH(PP)                                                                                       \
-  hipLaunchKernelGGL(q8_trimmed_reduce_kernel<PP>, grid, block, 0, s, recv, bps, (uint32_t)valid, f, K, live_mask, \
-                     inv, out_record, (unsigned long long*)counts, (unsigned long long*)nonfinite)
-  if (P <= 2)
-    VCX_Q8T_LAUNCH(2);
-  else if (P <= 4)
-    VCX_Q8T_LAUNCH(4);
-  else if (P <= 8)
-    VCX_Q8T_LAUNCH(8);
-  else
-    VCX_Q8T_LAUNCH(16);
-#undef VCX_Q8T_LAUNCH
+  for_padded_peers(P, [&](auto pp) {
+    hipLaunchKernelGGL(q8_trimmed_reduce_kernel<decltype(pp)::value>, grid, block, 0, s, recv, bps, (uint32_t)valid, f,
+                       K, live_mask, inv, out_record, (unsigned long long*)counts, (unsigned long long*)nonfinite);
+  });
 }
 
 int vcx_q8_trimmed_reduce_max_blocks() { return Q8_TRIMMED_MAX_BLOCKS; }

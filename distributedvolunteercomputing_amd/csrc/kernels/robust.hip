@@ -15,44 +15,13 @@
 // Only the two threshold keys are needed, not the sorted values, because the sum runs in row order:
 // a Batcher odd-even merge network sorts a copy of the keys (63 compare-exchanges at 16 rows), the
 // thresholds are picked from it by a chain of wave-uniform selects, and each row compares its own key
-// against them. Every array is indexed statically and stays in registers.
+// against them. Every array is indexed statically and stays in registers. The sorting network and what else the
+// cclip kernels below and the q8 robust reduce (compress.hip) use as well are in robust_common.h.
 //
 // No reference analog: the reference averages nothing.
-#include "vcx_common.h"
-
-#include <stdexcept>
-#include <string>
+#include "robust_common.h"
 
 namespace vcx {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int TR_MAX_P = 16;
-constexpr unsigned int TR_DEAD_KEY = 0xFFFFFFFFu;  // live keys stay below 2^24
-
-// Batcher's odd-even merge sort over N = 2^k keys, ascending; fully unrolled.
-template <int N>
-__host__ __device__ __forceinline__ void tr_sort(unsigned int (&a)[N]) {
-#pragma unroll
-  for (int p = 1; p < N; p *= 2) {
-#pragma unroll
-    for (int k = p; k >= 1; k /= 2) {
-#pragma unroll
-      for (int j = k % p; j + k < N; j += 2 * k) {
-#pragma unroll
-        for (int i = 0; i < k; ++i) {
-          const int x = i + j, y = i + j + k;
-          if (y < N && x / (2 * p) == y / (2 * p)) {
-            const unsigned int lo = a[x] < a[y] ? a[x] : a[y];
-            const unsigned int hi = a[x] < a[y] ? a[y] : a[x];
-            a[x] = lo;
-            a[y] = hi;
-          }
-        }
-      }
-    }
-  }
-}
 
 // PP: P padded to a power of two; rows P..PP-1 are never read and never written.
 template <int PP>
@@ -79,6 +48,7 @@ __global__ void __launch_bounds__(256) trimmed_reduce_bcast_bf16_kernel(const bf
     for (int j = 0; j < 8; ++j) {
       // keys in the form (s << 16) | row: the order of (s << 8) | row, built from the fp32 pattern of the value
       // with wave-uniform masks (scalar registers) in place of per-row selects
+      // (the value is extracted inline, not by tr_elem: through the helper PP = 16 compiles to other machine code)
       unsigned int val[PP], key[PP], srt[PP];
 #pragma unroll
       for (int k = 0; k < PP; ++k) {
@@ -103,10 +73,7 @@ __global__ void __launch_bounds__(256) trimmed_reduce_bcast_bf16_kernel(const bf
         t += kept ? __uint_as_float(val[k]) : 0.f;  // + (+0) leaves a sum that started at +0 unchanged
         cnt[k] += kept ? 0u : 1u;
       }
-      const float r = t * inv;
-      const bf16 h = (bf16)r;
-      unsigned int hb = (unsigned int)__builtin_bit_cast(unsigned short, h);
-      if (r != r) hb = 0x7FC0u;
+      const unsigned int hb = tr_bf16_bits(t * inv);
       if (j & 1)
         o[j >> 1] |= hb << 16;
       else
@@ -154,18 +121,6 @@ constexpr int CC_MAX_ITERS = 8;
 constexpr int CC_TILE = 512;  // chunk partials per row staged in LDS by the weights kernel
 
 __device__ __forceinline__ bool cc_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-
-__device__ __forceinline__ unsigned int cc_bf16_bits(float r) {
-  const bf16 h = (bf16)r;
-  unsigned int hb = (unsigned int)__builtin_bit_cast(unsigned short, h);
-  if (r != r) hb = 0x7FC0u;
-  return hb;
-}
-
-// fp32 pattern of element j (0..7) of a vector of 8 bf16
-__device__ __forceinline__ unsigned int cc_elem(const u32x4& raw, int j) {
-  return (j & 1) ? (raw[j >> 1] & 0xFFFF0000u) : (raw[j >> 1] << 16);
-}
 
 // The trimmed kernel's rule on one element position (val: the rows' fp32 patterns): (sum of the kept) * inv.
 template <int PP>
@@ -242,9 +197,9 @@ __global__ void __launch_bounds__(256) cclip_init_kernel(const bf16* __restrict_
       for (int j = 0; j < 8; ++j) {
         unsigned int val[PP];
 #pragma unroll
-        for (int k = 0; k < PP; ++k) val[k] = cc_elem(raw[k], j);
+        for (int k = 0; k < PP; ++k) val[k] = tr_elem(raw[k], j);
         const float r = cc_trimmed<PP>(val, f, K, live, inv);
-        const float c0 = __uint_as_float(cc_bf16_bits(r) << 16);  // the median rule's bf16 result, as fp32
+        const float c0 = __uint_as_float(tr_bf16_bits(r) << 16);  // the median rule's bf16 result, as fp32
         vv[j] = c0;
         const bool fin = cc_finite(c0);
 #pragma unroll
@@ -359,7 +314,7 @@ __global__ void __launch_bounds__(256) cclip_step_kernel(const bf16* in, bf16* o
         const float c0 = vv[j];
         float x[PP];
 #pragma unroll
-        for (int k = 0; k < PP; ++k) x[k] = __uint_as_float(cc_elem(raw[k], j));
+        for (int k = 0; k < PP; ++k) x[k] = __uint_as_float(tr_elem(raw[k], j));
         float t = 0.f;
 #pragma unroll
         for (int k = 0; k < PP; ++k) {
@@ -369,7 +324,7 @@ __global__ void __launch_bounds__(256) cclip_step_kernel(const bf16* in, bf16* o
         const float c1 = cc_finite(c0) ? c0 + t * inv_k : c0;
         vv[j] = c1;
         if (LAST) {
-          const unsigned int hb = cc_bf16_bits(c1);
+          const unsigned int hb = tr_bf16_bits(c1);
           if (j & 1)
             o[j >> 1] |= hb << 16;
           else
@@ -416,35 +371,21 @@ using namespace vcx;
 // A call the kernel cannot take raises before anything is launched.
 void vcx_trimmed_reduce_bcast_bf16(const void* in, void* out, void* mine, int P, int64_t n, int trim,
                                    uint32_t live_mask, float inv, int64_t* counts, hipStream_t s) {
-  const char* who = "trimmed_reduce_bcast_bf16";
-  if (P < 1 || P > TR_MAX_P)
-    throw std::invalid_argument(std::string(who) + ": P must be in 1..16, got " + std::to_string(P));
-  if (live_mask == 0 || (P < 32 && (live_mask >> P) != 0))
-    throw std::invalid_argument(std::string(who) + ": live_mask must name at least one of the P rows and no other");
-  if (n < 0 || n % 8 != 0)
-    throw std::invalid_argument(std::string(who) + ": n must be a multiple of 8, got " + std::to_string(n));
-  if (trim < 0) throw std::invalid_argument(std::string(who) + ": trim must be >= 0");
+  const std::string who = "trimmed_reduce_bcast_bf16";
+  check_rows(who, P, live_mask);
+  if (n < 0 || n % 8 != 0) throw std::invalid_argument(who + ": n must be a multiple of 8, got " + std::to_string(n));
+  if (trim < 0) throw std::invalid_argument(who + ": trim must be >= 0");
   if (!in || ((uintptr_t)in & 15) || ((uintptr_t)out & 15) || ((uintptr_t)mine & 15))
-    throw std::invalid_argument(std::string(who) + ": in, out and mine must be 16-byte aligned");
-  if ((uintptr_t)counts & 7) throw std::invalid_argument(std::string(who) + ": counts must be 8-byte aligned");
+    throw std::invalid_argument(who + ": in, out and mine must be 16-byte aligned");
+  if ((uintptr_t)counts & 7) throw std::invalid_argument(who + ": counts must be 8-byte aligned");
   if (n == 0) return;
-  const int K = __builtin_popcount(live_mask);
-  const int f = trim < (K - 1) / 2 ? trim : (K - 1) / 2;
+  const int K = __builtin_popcount(live_mask), f = trim_of(trim, K);
   const int64_t n8 = n / 8;
   const dim3 grid(stream_grid(n8, 256)), block(256);
-  unsigned long long* c = (unsigned long long*)counts;
-#define VCX_TR_LAUNCH(PP)                                                                                     \
-  hipLaunchKernelGGL(trimmed_reduce_bcast_bf16_kernel<PP>, grid, block, 0, s, (const bf16*)in, (bf16*)out, \
-                     (bf16*)mine, P, n8, f, K, live_mask, inv, c)
-  if (P <= 2)
-    VCX_TR_LAUNCH(2);
-  else if (P <= 4)
-    VCX_TR_LAUNCH(4);
-  else if (P <= 8)
-    VCX_TR_LAUNCH(8);
-  else
-    VCX_TR_LAUNCH(16);
-#undef VCX_TR_LAUNCH
+  for_padded_peers(P, [&](auto pp) {
+    hipLaunchKernelGGL(trimmed_reduce_bcast_bf16_kernel<decltype(pp)::value>, grid, block, 0, s, (const bf16*)in,
+                       (bf16*)out, (bf16*)mine, P, n8, f, K, live_mask, inv, (unsigned long long*)counts);
+  });
 }
 
 
@@ -458,22 +399,18 @@ int64_t vcx_cclip_workspace_floats(int P, int64_t n) {
 // A call the kernels cannot take raises before anything is launched.
 void vcx_cclip_reduce_bcast_bf16(const void* in, void* out, void* mine, int P, int64_t n, uint32_t live_mask, float tau,
                                  int iters, float* weights, float* workspace, hipStream_t s) {
-  const char* who = "cclip_reduce_bcast_bf16";
-  if (P < 1 || P > TR_MAX_P)
-    throw std::invalid_argument(std::string(who) + ": P must be in 1..16, got " + std::to_string(P));
-  if (live_mask == 0 || (P < 32 && (live_mask >> P) != 0))
-    throw std::invalid_argument(std::string(who) + ": live_mask must name at least one of the P rows and no other");
-  if (n < 0 || n % 8 != 0)
-    throw std::invalid_argument(std::string(who) + ": n must be a multiple of 8, got " + std::to_string(n));
+  const std::string who = "cclip_reduce_bcast_bf16";
+  check_rows(who, P, live_mask);
+  if (n < 0 || n % 8 != 0) throw std::invalid_argument(who + ": n must be a multiple of 8, got " + std::to_string(n));
   if (!(tau >= 0.f) || tau > 3.402823466e38f)
-    throw std::invalid_argument(std::string(who) + ": tau must be finite and >= 0 (0: adaptive)");
+    throw std::invalid_argument(who + ": tau must be finite and >= 0 (0: adaptive)");
   if (iters < 1 || iters > CC_MAX_ITERS)
-    throw std::invalid_argument(std::string(who) + ": iters must be in 1..8, got " + std::to_string(iters));
+    throw std::invalid_argument(who + ": iters must be in 1..8, got " + std::to_string(iters));
   if (!in || ((uintptr_t)in & 15) || ((uintptr_t)out & 15) || ((uintptr_t)mine & 15))
-    throw std::invalid_argument(std::string(who) + ": in, out and mine must be 16-byte aligned");
+    throw std::invalid_argument(who + ": in, out and mine must be 16-byte aligned");
   if (!workspace || ((uintptr_t)workspace & 15))
-    throw std::invalid_argument(std::string(who) + ": workspace must be 16-byte aligned");
-  if ((uintptr_t)weights & 3) throw std::invalid_argument(std::string(who) + ": weights must be 4-byte aligned");
+    throw std::invalid_argument(who + ": workspace must be 16-byte aligned");
+  if ((uintptr_t)weights & 3) throw std::invalid_argument(who + ": weights must be 4-byte aligned");
   if (n == 0) return;
   const int K = __builtin_popcount(live_mask);
   const int64_t n8 = n / 8;
@@ -482,37 +419,27 @@ void vcx_cclip_reduce_bcast_bf16(const void* in, void* out, void* mine, int P, i
                        (bf16*)out, (bf16*)mine, P, n8, __builtin_ctz(live_mask), weights);
     return;
   }
-  const int f = (K - 1) / 2;  // the median rule is the start
-  // the fp32 values of 1 / (K - 2f) and 1 / K as ops/robust.py forms them: the double quotient, rounded once more
-  const float inv = (float)(1.0 / (double)(K - 2 * f)), inv_k = (float)(1.0 / (double)K);
+  const int f = trim_of(TR_MAX_P, K);  // the median rule is the start: all the trim that K voters allow
+  const float inv = trim_inv(K, f), inv_k = trim_inv(K, 0);
   const int64_t nchunks = (n8 + CC_CHUNK_VEC - 1) / CC_CHUNK_VEC;
   float* v = workspace;
   float* part = v + n;
   float* w = part + (int64_t)P * nchunks;
   const dim3 grid((unsigned int)(nchunks < CC_MAX_BLOCKS ? nchunks : CC_MAX_BLOCKS)), block(256);
-#define VCX_CC_RUN(PP)                                                                                               \
-  do {                                                                                                               \
-    hipLaunchKernelGGL(cclip_init_kernel<PP>, grid, block, 0, s, (const bf16*)in, v, part, n8, nchunks, f, K,        \
-                       live_mask, inv);                                                                              \
-    for (int l = 0; l < iters; ++l) {                                                                                \
-      const bool last = l == iters - 1;                                                                              \
-      hipLaunchKernelGGL(cclip_weights_kernel<PP>, dim3(1), block, 0, s, part, nchunks, P, K, live_mask, tau, w,     \
-                         last ? weights : (float*)nullptr);                                                          \
-      if (last)                                                                                                      \
-        hipLaunchKernelGGL((cclip_step_kernel<PP, true>), grid, block, 0, s, (const bf16*)in, (bf16*)out,            \
-                           (bf16*)mine, v, w, part, P, n8, nchunks, live_mask, inv_k);                               \
-      else                                                                                                           \
-        hipLaunchKernelGGL((cclip_step_kernel<PP, false>), grid, block, 0, s, (const bf16*)in, (bf16*)out,           \
-                           (bf16*)mine, v, w, part, P, n8, nchunks, live_mask, inv_k);                               \
-    }                                                                                                                \
-  } while (0)
-  if (P <= 2)
-    VCX_CC_RUN(2);
-  else if (P <= 4)
-    VCX_CC_RUN(4);
-  else if (P <= 8)
-    VCX_CC_RUN(8);
-  else
-    VCX_CC_RUN(16);
-#undef VCX_CC_RUN
+  for_padded_peers(P, [&](auto pp) {
+    constexpr int PP = decltype(pp)::value;
+    hipLaunchKernelGGL(cclip_init_kernel<PP>, grid, block, 0, s, (const bf16*)in, v, part, n8, nchunks, f, K,
+                       live_mask, inv);
+    for (int l = 0; l < iters; ++l) {
+      const bool last = l == iters - 1;
+      hipLaunchKernelGGL(cclip_weights_kernel<PP>, dim3(1), block, 0, s, part, nchunks, P, K, live_mask, tau, w,
+                         last ? weights : (float*)nullptr);
+      if (last)
+        hipLaunchKernelGGL((cclip_step_kernel<PP, true>), grid, block, 0, s, (const bf16*)in, (bf16*)out,
+                           (bf16*)mine, v, w, part, P, n8, nchunks, live_mask, inv_k);
+      else
+        hipLaunchKernelGGL((cclip_step_kernel<PP, false>), grid, block, 0, s, (const bf16*)in, (bf16*)out,
+                           (bf16*)mine, v, w, part, P, n8, nchunks, live_mask, inv_k);
+    }
+  });
 }

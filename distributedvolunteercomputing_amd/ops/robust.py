@@ -97,12 +97,16 @@ def effective_trim(aggregate: str, trim: int, K: int) -> int:
     raise ValueError(f"unknown aggregation rule {aggregate!r}; choose from {AGGREGATES}")
 
 
+def _check_rows(who: str, P: int, live_mask: int):
+    if not 1 <= P <= MAX_PEERS:
+        raise ValueError(f"{who}: P must be in 1..{MAX_PEERS}, got {P}")
+    if live_mask <= 0 or live_mask >> P:
+        raise ValueError(f"{who}: live_mask {live_mask:#x} must name at least one of the {P} rows and no other")
+
+
 def trim_plan(P: int, trim: int, live_mask: int):
     """(K, f, inv) of one call, after the checks every path shares."""
-    if not 1 <= P <= MAX_PEERS:
-        raise ValueError(f"trimmed mean: P must be in 1..{MAX_PEERS}, got {P}")
-    if live_mask <= 0 or live_mask >> P:
-        raise ValueError(f"trimmed mean: live_mask {live_mask:#x} must name at least one of the {P} rows and no other")
+    _check_rows("trimmed mean", P, live_mask)
     if trim < 0:
         raise ValueError(f"trimmed mean: trim must be >= 0, got {trim}")
     K = bin(live_mask).count("1")
@@ -153,13 +157,16 @@ def trimmed_mean_reference(x: torch.Tensor, trim: int, live_mask: int | None = N
         if (live_mask >> k) & 1:
             acc = acc + torch.where(kept[k], x[k].float(), zero)
     res = acc * torch.tensor(inv, dtype=torch.float32, device=x.device)
-    # the canonical NaN goes in by its bit pattern, after the rounding: torch's own fp32 -> bf16 turns a NaN
-    # into 0x7FC0 or 0xFFFF depending on the code path (scalar or vectorised) that converts the element
-    nan_bits = torch.tensor([0x7FC0 if x.dtype == torch.bfloat16 else 0x7FC00000], device=x.device,
-                            dtype=torch.int16 if x.dtype == torch.bfloat16 else torch.int32)
-    res = torch.where(torch.isnan(res), nan_bits.view(x.dtype), res.to(x.dtype))
     counts = (live & ~kept).sum(dim=1).to(torch.int64)
-    return res, counts
+    return _canonical(res, x.dtype), counts
+
+
+def _write_result(res, out, mine, P: int):
+    """res [n] to every row of `out` [P, n] and to `mine` [n], where they are given."""
+    if out is not None:
+        out.view(P, -1).copy_(res.unsqueeze(0).expand(P, -1))
+    if mine is not None:
+        mine.copy_(res)
 
 
 def trimmed_reduce_bcast_bf16(inp, out, mine, P: int, trim: int, live_mask: int | None = None, counts=None):
@@ -175,10 +182,7 @@ def trimmed_reduce_bcast_bf16(inp, out, mine, P: int, trim: int, live_mask: int 
         native().trimmed_reduce_bcast_bf16(inp, out, mine, P, f, live_mask, inv, counts)
         return
     res, c = trimmed_mean_reference(inp.view(P, -1), f, live_mask)
-    if out is not None:
-        out.view(P, -1).copy_(res.unsqueeze(0).expand(P, -1))
-    if mine is not None:
-        mine.copy_(res)
+    _write_result(res, out, mine, P)
     if counts is not None:
         counts.add_(c.to(counts.device))
 
@@ -186,10 +190,7 @@ def trimmed_reduce_bcast_bf16(inp, out, mine, P: int, trim: int, live_mask: int 
 # ------------------------------------------------------------------------------ centered clipping
 def cclip_plan(P: int, live_mask: int, tau: float, iters: int) -> int:
     """K of one centered-clipping call, after the checks every path shares."""
-    if not 1 <= P <= MAX_PEERS:
-        raise ValueError(f"cclip: P must be in 1..{MAX_PEERS}, got {P}")
-    if live_mask <= 0 or live_mask >> P:
-        raise ValueError(f"cclip: live_mask {live_mask:#x} must name at least one of the {P} rows and no other")
+    _check_rows("cclip", P, live_mask)
     check_clip(tau, iters)
     return bin(live_mask).count("1")
 
@@ -231,7 +232,9 @@ def _fp32(a: float) -> float:
 
 
 def _canonical(v: torch.Tensor, dtype) -> torch.Tensor:
-    """round_to_dtype(v) with a NaN written as the canonical quiet NaN (see trimmed_mean_reference)."""
+    """round_to_dtype(v) with a NaN written as the canonical quiet NaN."""
+    # the canonical NaN goes in by its bit pattern, after the rounding: torch's own fp32 -> bf16 turns a NaN
+    # into 0x7FC0 or 0xFFFF depending on the code path (scalar or vectorised) that converts the element
     nan_bits = torch.tensor([0x7FC0 if dtype == torch.bfloat16 else 0x7FC00000], device=v.device,
                             dtype=torch.int16 if dtype == torch.bfloat16 else torch.int32)
     return torch.where(torch.isnan(v), nan_bits.view(dtype), v.to(dtype))
@@ -296,9 +299,6 @@ def cclip_reduce_bcast_bf16(inp, out, mine, P: int, tau: float, iters: int, live
         native().cclip_reduce_bcast_bf16(inp, out, mine, P, live_mask, float(tau), iters, weights)
         return
     res, w, _ = centered_clip_reference(inp.view(P, -1), live_mask, tau, iters)
-    if out is not None:
-        out.view(P, -1).copy_(res.unsqueeze(0).expand(P, -1))
-    if mine is not None:
-        mine.copy_(res)
+    _write_result(res, out, mine, P)
     if weights is not None:
         weights.copy_(w)

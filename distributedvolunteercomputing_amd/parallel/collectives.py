@@ -194,26 +194,44 @@ def _ring(t, group):
     return t
 
 
-def _direct(t, group):
+def _direct_len(t, P):
+    """Padded length of `t` in the direct exchange: P shards of equal length (bf16: a multiple of 8 each)."""
+    return _pad_len(t.numel(), P, 8 if t.dtype == torch.bfloat16 else 1)
+
+
+def _direct_exchange(t, group, middle, side=None):
+    """`direct`'s exchange around a middle step, in place: pad, one all-to-all that brings every peer's copy of MY
+    shard, `middle(recv, mine, P)`, one all-to-all that returns the shards. `recv` is [P, m] flat, row j = peer j's
+    copy of my shard; `mine` is my shard of the buffer, which the middle step fills; it returns the send buffer,
+    [P, m] flat, row j = what goes back to peer j (`recv` itself when it wrote there). `side`: a small per-rank
+    tensor the middle step filled, summed over the group on the device the backend works on, and returned."""
     P, r = group.size, group.rank
     n = t.numel()
-    L = _pad_len(n, P, 8 if t.dtype == torch.bfloat16 else 1)
-    buf = _padded(t, L)
-    m = L // P
+    buf = _padded(t, _direct_len(t, P))
+    m = buf.numel() // P
     split = [m] * P
-    recv = torch.empty_like(buf)  # [P, m]: row j = peer j's copy of MY shard
+    recv = torch.empty_like(buf)
     group.alltoall_(recv, buf, split, split)
-    send = recv  # reused: row j = the reduced shard, sent back to peer j
-    mine = buf[r * m : (r + 1) * m]
-    if buf.is_cuda and buf.dtype == torch.bfloat16:
-        ops.reduce_bcast_bf16(recv, send, mine, P)
-    else:
-        red = recv.view(P, m).sum(0, dtype=torch.float32 if buf.dtype != torch.float64 else None).to(buf.dtype)
-        mine.copy_(red)
-        send = red.unsqueeze(0).expand(P, m).contiguous().view(-1)
+    send = middle(recv, buf[r * m : (r + 1) * m], P)
     group.alltoall_(buf, send, split, split)
+    if side is not None:
+        side = side.to(group.device if group.backend == "nccl" else "cpu")
+        group.allreduce_(side)
     if buf is not t:
         t.copy_(buf[:n])
+    return side
+
+
+def _direct(t, group):
+    def middle(recv, mine, P):
+        if recv.is_cuda and recv.dtype == torch.bfloat16:
+            ops.reduce_bcast_bf16(recv, recv, mine, P)  # recv reused as the send buffer
+            return recv
+        red = recv.view(P, -1).sum(0, dtype=torch.float32 if recv.dtype != torch.float64 else None).to(recv.dtype)
+        mine.copy_(red)
+        return red.unsqueeze(0).expand(P, -1).contiguous().view(-1)
+
+    _direct_exchange(t, group, middle)
     return t
 
 
@@ -224,36 +242,29 @@ def robust_mean_(t: torch.Tensor, group: PeerGroup, trim: int, live_ranks=None) 
     ranks that vote (default all); the others send their buffer and receive the result like everyone.
     Returns counts (int64 [P], identical on every rank): per rank, how many of its elements were
     trimmed over the whole buffer."""
-    if group is None or group.size == 1:
-        P, r = 1, 0
-    else:
-        P, r = group.size, group.rank
+    P = 1 if group is None else group.size
     mask = robust.mask_of(live_ranks, P)
     n = t.numel()
-    L = _pad_len(n, P, 8 if t.dtype == torch.bfloat16 else 1)
-    buf = _padded(t, L)
-    m = L // P
-    split = [m] * P
-    counts = torch.zeros(P, dtype=torch.int64, device=buf.device)
+    counts = torch.zeros(P, dtype=torch.int64, device=t.device)
     if P == 1:
+        buf = _padded(t, _direct_len(t, 1))
         ops.trimmed_reduce_bcast_bf16(buf, None, buf, 1, trim, mask, counts)
+        if buf is not t:
+            t.copy_(buf[:n])
     else:
-        recv = torch.empty_like(buf)  # [P, m]: row j = peer j's copy of MY shard
-        group.alltoall_(recv, buf, split, split)
-        mine = buf[r * m : (r + 1) * m]
-        ops.trimmed_reduce_bcast_bf16(recv, recv, mine, P, trim, mask, counts)  # recv reused as the send buffer
-        group.alltoall_(buf, recv, split, split)
-        counts = counts.to(group.device if group.backend == "nccl" else "cpu")
-        group.allreduce_(counts)
-    if L != n:
+        def middle(recv, mine, P):
+            ops.trimmed_reduce_bcast_bf16(recv, recv, mine, P, trim, mask, counts)  # recv reused as the send buffer
+            return recv
+
+        counts = _direct_exchange(t, group, middle, counts)
+    pad = _direct_len(t, P) - n
+    if pad:
         # every voter's padding is +0, a tie that goes to the row: its f lowest and f highest voters
         # were "trimmed" there, which says nothing about them
         _, f, _ = robust.trim_plan(P, trim, mask)
         voters = [k for k in range(P) if (mask >> k) & 1]
         for k in (voters[:f] + voters[len(voters) - f:]) if f else ():
-            counts[k] -= L - n
-    if buf is not t:
-        t.copy_(buf[:n])
+            counts[k] -= pad
     return counts
 
 
@@ -268,23 +279,12 @@ def cclip_mean_(t: torch.Tensor, group: PeerGroup, tau: float, iters: int, live_
     if group is None or group.size == 1:
         robust.mask_of(live_ranks, 1)
         return torch.ones(1, dtype=torch.float32)
-    P, r = group.size, group.rank
-    mask = robust.mask_of(live_ranks, P)
-    robust.cclip_plan(P, mask, tau, iters)
-    n = t.numel()
-    L = _pad_len(n, P, 8 if t.dtype == torch.bfloat16 else 1)
-    buf = _padded(t, L)
-    m = L // P
-    split = [m] * P
-    weights = torch.zeros(P, dtype=torch.float32, device=buf.device)
-    recv = torch.empty_like(buf)  # [P, m]: row j = peer j's copy of MY shard
-    group.alltoall_(recv, buf, split, split)
-    mine = buf[r * m : (r + 1) * m]
-    ops.cclip_reduce_bcast_bf16(recv, recv, mine, P, tau, iters, mask, weights)  # recv reused as the send buffer
-    group.alltoall_(buf, recv, split, split)
-    weights = weights.to(group.device if group.backend == "nccl" else "cpu")
-    group.allreduce_(weights)
-    weights.div_(P)
-    if buf is not t:
-        t.copy_(buf[:n])
-    return weights
+    mask = robust.mask_of(live_ranks, group.size)
+    robust.cclip_plan(group.size, mask, tau, iters)
+    weights = torch.zeros(group.size, dtype=torch.float32, device=t.device)
+
+    def middle(recv, mine, P):
+        ops.cclip_reduce_bcast_bf16(recv, recv, mine, P, tau, iters, mask, weights)  # recv reused as the send buffer
+        return recv
+
+    return _direct_exchange(t, group, middle, weights).div_(group.size)

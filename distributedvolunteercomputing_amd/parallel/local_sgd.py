@@ -23,6 +23,7 @@ Reference analog: the chunk (100 frames) is the reference's unit of independent 
 """
 from __future__ import annotations
 
+import contextlib
 import time
 from dataclasses import dataclass, field
 
@@ -320,14 +321,21 @@ class LocalSGDTrainer:
         if self.compressor is not None:
             avg = self.compressor.allreduce_mean(self.delta, g)
             return avg, g.size / contributors
-        if self.time_reduce:
-            self._dev_sync()
-            t0 = time.perf_counter()
-        allreduce_sum_(self.delta, g, self.cfg.algo)
-        if self.time_reduce:
-            self._dev_sync()
-            self.reduce_log.append(((time.perf_counter() - t0) * 1e3, self.delta.numel() * self.delta.element_size()))
+        with self._timed_reduce():
+            allreduce_sum_(self.delta, g, self.cfg.algo)
         return self.delta, 1.0 / contributors
+
+    @contextlib.contextmanager
+    def _timed_reduce(self):
+        """Under `time_reduce`: the collective inside, between two device synchronisations, goes into `reduce_log`."""
+        if not self.time_reduce:
+            yield
+            return
+        self._dev_sync()
+        t0 = time.perf_counter()
+        yield
+        self._dev_sync()
+        self.reduce_log.append(((time.perf_counter() - t0) * 1e3, self.delta.numel() * self.delta.element_size()))
 
     @staticmethod
     def _voters(g, newcomers):
@@ -344,14 +352,8 @@ class LocalSGDTrainer:
         live = self._voters(g, newcomers)
         K = g.size if live is None else len(live)
         if c.aggregate == "cclip":
-            if self.time_reduce:
-                self._dev_sync()
-                t0 = time.perf_counter()
-            w = cclip_mean_(self.delta, g, c.clip_tau, c.clip_iters, live)
-            if self.time_reduce:
-                self._dev_sync()
-                self.reduce_log.append(((time.perf_counter() - t0) * 1e3,
-                                        self.delta.numel() * self.delta.element_size()))
+            with self._timed_reduce():
+                w = cclip_mean_(self.delta, g, c.clip_tau, c.clip_iters, live)
             self.clip_weight = w.tolist()
             return self.delta, 1.0
         trim = effective_trim(c.aggregate, c.trim, K)
@@ -364,13 +366,8 @@ class LocalSGDTrainer:
             self.trim_share = (counts.double() / self.delta.numel()).tolist()
             self.nonfinite_share = nonfinite / self.delta.numel()
             return avg, 1.0
-        if self.time_reduce:
-            self._dev_sync()
-            t0 = time.perf_counter()
-        counts = robust_mean_(self.delta, g, trim, live)
-        if self.time_reduce:
-            self._dev_sync()
-            self.reduce_log.append(((time.perf_counter() - t0) * 1e3, self.delta.numel() * self.delta.element_size()))
+        with self._timed_reduce():
+            counts = robust_mean_(self.delta, g, trim, live)
         self.trim_share = (counts.double() / self.delta.numel()).tolist()
         return self.delta, 1.0
 

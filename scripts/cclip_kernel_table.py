@@ -7,40 +7,14 @@ GPT-2-small (124M) and of a 268M-element buffer on P = 4 and 8 peers.
 
 Needs the GPU: there is nothing to time without one.
 """
-import argparse
-import statistics
-import sys
-from pathlib import Path
-
 import torch
 
-sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from _kernel_table import BUFFERS, parse_args, time_interleaved, write_table
 
-from distributedvolunteercomputing_amd import ops  # noqa: E402
+from distributedvolunteercomputing_amd import ops  # noqa: E402  (_kernel_table put the repository on the path)
 from distributedvolunteercomputing_amd.ops import robust  # noqa: E402
 
-BUFFERS = (("gpt2-small 124M", 124_439_808), ("268M", 268_435_456))
-PEERS = (4, 8)
 ITERS = (1, 3)
-
-
-def _time(fn, reps, warmup=3):
-    """Median / min ms per call of each fn in `fn` (a dict), calls interleaved."""
-    for _ in range(warmup):
-        for f in fn.values():
-            f()
-    torch.cuda.synchronize()
-    ev = {k: [] for k in fn}
-    for _ in range(reps):
-        for k, f in fn.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            f()
-            b.record()
-            ev[k].append((a, b))
-    torch.cuda.synchronize()
-    ms = {k: [a.elapsed_time(b) for a, b in v] for k, v in ev.items()}
-    return {k: (statistics.median(v), min(v)) for k, v in ms.items()}
 
 
 def cclip_bytes(P: int, n: int, L: int) -> int:
@@ -51,12 +25,7 @@ def cclip_bytes(P: int, n: int, L: int) -> int:
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--out", default="profiles/cclip_reduce.txt")
-    ap.add_argument("--reps", type=int, default=30)
-    a = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        raise SystemExit("cclip_kernel_table: no GPU, nothing measured")
+    a = parse_args(__file__, __doc__, "profiles/cclip_reduce.txt", 30, argv)
     ops.native()
     dev = torch.device("cuda", 0)
     lines = [f"# {torch.cuda.get_device_name(0)}; median of {a.reps} calls each, interleaved, device events",
@@ -64,7 +33,7 @@ def main(argv=None):
              f"{'buffer':16s} {'P':>2s} {'n per shard':>11s} {'call':26s} {'launches':>8s} {'median us':>10s} "
              f"{'min us':>9s} {'MB moved':>9s} {'TB/s':>6s} {'vs trimmed':>10s} {'vs (L+1) trimmed':>16s}"]
     for name, total in BUFFERS:
-        for P in PEERS:
+        for P in a.peers:
             n = total // P // 8 * 8
             g = torch.Generator(device=dev).manual_seed(P)
             inp = (0.01 * torch.randn(P * n, device=dev, generator=g)).to(torch.bfloat16)
@@ -79,7 +48,7 @@ def main(argv=None):
                 fns[f"cclip L={L} adaptive tau"] = (
                     lambda L=L: ops.cclip_reduce_bcast_bf16(inp, out, mine, P, 0.0, L, None, w),
                     2 * L + 1, cclip_bytes(P, n, L), L)
-            res = _time({k: v[0] for k, v in fns.items()}, a.reps)
+            res = time_interleaved({k: v[0] for k, v in fns.items()}, a.reps, warmup=3)
             base = res["trimmed median"][0]
             for k, (med, mn) in res.items():
                 _, launches, moved, L = fns[k]
@@ -91,10 +60,7 @@ def main(argv=None):
                          f"{(res['cclip L=3 adaptive tau'][0] - res['cclip L=1 adaptive tau'][0]) * 500:.1f} us per "
                          f"(weights + step) pair that is not the last")
             del inp, out, mine
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(a.out).write_text(text)
+    write_table(lines, a.out)
 
 
 if __name__ == "__main__":

@@ -6,48 +6,16 @@ repetitions. Shapes: the shard of a GPT-2-small (124M) and of a 268M-element buf
 
 Needs the GPU: there is nothing to time without one.
 """
-import argparse
-import statistics
-import sys
-from pathlib import Path
-
 import torch
 
-sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from _kernel_table import BUFFERS, parse_args, time_interleaved, write_table
 
-from distributedvolunteercomputing_amd import ops  # noqa: E402
+from distributedvolunteercomputing_amd import ops  # noqa: E402  (_kernel_table put the repository on the path)
 from distributedvolunteercomputing_amd.parallel.compression import Quant8Compressor  # noqa: E402
-
-BUFFERS = (("gpt2-small 124M", 124_439_808), ("268M", 268_435_456))
-PEERS = (4, 8)
-
-
-def _time(fn, reps, warmup=5):
-    """Median / min ms per launch of each fn in `fn` (a dict), launches interleaved."""
-    for _ in range(warmup):
-        for f in fn.values():
-            f()
-    torch.cuda.synchronize()
-    ev = {k: [] for k in fn}
-    for _ in range(reps):
-        for k, f in fn.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            f()
-            b.record()
-            ev[k].append((a, b))
-    torch.cuda.synchronize()
-    ms = {k: [a.elapsed_time(b) for a, b in v] for k, v in ev.items()}
-    return {k: (statistics.median(v), min(v)) for k, v in ms.items()}
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--out", default="profiles/q8_robust_reduce.txt")
-    ap.add_argument("--reps", type=int, default=40)
-    a = ap.parse_args(argv)
-    if not torch.cuda.is_available():
-        raise SystemExit("q8_robust_kernel_table: no GPU, nothing measured")
+    a = parse_args(__file__, __doc__, "profiles/q8_robust_reduce.txt", 40, argv)
     C = ops.native()
     dev = torch.device("cuda", 0)
     lines = [f"# {torch.cuda.get_device_name(0)}; median of {a.reps} launches each, interleaved, device events",
@@ -55,7 +23,7 @@ def main(argv=None):
              f"{'buffer':16s} {'P':>2s} {'m per shard':>11s} {'kernel':28s} {'median us':>10s} {'min us':>9s} "
              f"{'MB moved':>9s} {'TB/s':>6s} {'vs q8_reduce':>12s}"]
     for name, total in BUFFERS:
-        for P in PEERS:
+        for P in a.peers:
             comp = Quant8Compressor(total, dev)
             L, m, rec = comp.layout(P)
             g = torch.Generator(device=dev).manual_seed(P)
@@ -74,17 +42,14 @@ def main(argv=None):
                 "trimmed median": lambda: C.q8_trimmed_reduce(recv, P, m, (P - 1) // 2, mask, m, out, counts, bad),
                 "trimmed trim=1, no counters": lambda: C.q8_trimmed_reduce(recv, P, m, 1, mask, m, out),
             }
-            res = _time(fns, a.reps)
+            res = time_interleaved(fns, a.reps)
             moved = (P + 1) * 1.03125 * m
             base = res["q8_reduce (sum)"][0]
             for k, (med, mn) in res.items():
                 lines.append(f"{name:16s} {P:2d} {m:11d} {k:28s} {med * 1e3:10.1f} {mn * 1e3:9.1f} {moved / 1e6:9.1f} "
                              f"{moved / (med * 1e-3) / 1e12:6.2f} {med / base:12.2f}")
             del recv, out
-    text = "\n".join(lines) + "\n"
-    print(text, end="")
-    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(a.out).write_text(text)
+    write_table(lines, a.out)
 
 
 if __name__ == "__main__":

@@ -47,6 +47,15 @@ class RuntimeConfig:
     # VCX_LMHEAD_DGRAD_NT: wte^T joins the batched transposes and the LM head's input gradient is the NT library
     # GEMM on it (GPT-2-small: 3.28 + 0.03 ms against 3.83 ms for the NN form); needs bwd_batch
     lmhead_dgrad_nt: bool = True
+    # VCX_DGRAD_NT_ATTN: with the batched W^T at hand, the qkv and attention-output input gradients are NT library
+    # GEMMs on it instead of gemm_ps (169.3 vs 196.2 us and 70.3 vs 75.0 us in isolation; in the step 1118.8-1122.4
+    # vs 1108.8-1113.2 samples/s, profiles/colsum_defer_step_kernels.txt); needs bwd_batch
+    dgrad_nt_attn: bool = True
+    # VCX_COLSUM_DEFER: inside ops.deferred_colsums() (the trainer's backward) the bias and LayerNorm column sums
+    # are finished once per backward pass by colsum_finish_many instead of per call site (ops/_deferred.py): 86 -> 4
+    # launches, 0.42 -> 0.08 ms of kernels, 231 MB of persistent partial rows at the GPT-2-small bench shape; alone
+    # it measured even with the parent (same file)
+    colsum_defer: bool = True
     # VCX_GEMM_FWD: forward GEMMs x W^T (+ b) and input gradients dY W of the linear layers on "lib" or "vcx"
     # (csrc/kernels/gemm_f.hip, opt-in: 0.85-0.93x the library at the GPT-2 shapes, profiles/r6_gemm_f.txt)
     gemm_fwd: str = "lib"
@@ -132,6 +141,8 @@ _ENV = {
     "bwd_batch": ("VCX_BWD_BATCH", _bool),
     "fc_dgrad_nt": ("VCX_FC_DGRAD_NT", _bool),
     "lmhead_dgrad_nt": ("VCX_LMHEAD_DGRAD_NT", _bool),
+    "dgrad_nt_attn": ("VCX_DGRAD_NT_ATTN", _bool),
+    "colsum_defer": ("VCX_COLSUM_DEFER", _bool),
     "narrow_gemm": ("VCX_NARROW_GEMM", str),
     "resnet_conv1x1": ("VCX_RESNET_CONV1X1", str),
     "resnet_bn": ("VCX_RESNET_BN", str),

@@ -754,7 +754,7 @@ at::Tensor grad_out(const c10::optional<at::Tensor>& given, int64_t n, const at:
 std::vector<at::Tensor> ln_bwd(at::Tensor dy, at::Tensor x, at::Tensor w, at::Tensor mean, at::Tensor rstd,
                                c10::optional<at::Tensor> dres, bool has_bias, bool rms, bool has_bb,
                                c10::optional<at::Tensor> dw_out, c10::optional<at::Tensor> db_out,
-                               c10::optional<at::Tensor> dbb_out) {
+                               c10::optional<at::Tensor> dbb_out, c10::optional<at::Tensor> parts, bool defer) {
   CHECK_IN(dy, kBF);
   CHECK_IN(x, kBF);
   CHECK_IN(w, kBF);
@@ -769,26 +769,97 @@ std::vector<at::Tensor> ln_bwd(at::Tensor dy, at::Tensor x, at::Tensor w, at::Te
     TORCH_CHECK(dres->sizes() == x.sizes());
   }
   const int P = vcx_ln_bwd_partials((int)R, C);
+  // parts: the caller's [n, P, C] fp32 partial rows (dw, then db and dbb when present) instead of fresh ones;
+  // defer: the partials are left unreduced for a later colsum_finish_many (the caller keeps `parts` alive)
+  const int64_t nparts = 1 + (has_bias ? 1 : 0) + (has_bb ? 1 : 0);
+  if (parts) {
+    CHECK_IN((*parts), kF);
+    TORCH_CHECK(parts->dim() == 3 && parts->size(0) == nparts && parts->size(1) == P && parts->size(2) == C,
+                "ln_bwd: parts must be [outputs, ln_bwd_partials(R, C), C] fp32");
+  }
+  TORCH_CHECK(!defer || parts, "ln_bwd: defer needs the caller's parts");
+  int64_t slot = 0;
+  auto part_rows = [&]() { return parts ? parts->select(0, slot++) : at::empty({P, C}, x.options().dtype(kF)); };
   auto dx = at::empty_like(x);
-  auto dw_part = at::empty({P, C}, x.options().dtype(kF));
+  auto dw_part = part_rows();
   int mask = 0;
   at::Tensor dw = grad_out(dw_out, C, x, &mask, 0);
   at::Tensor db_part, db;
   if (has_bias) {
-    db_part = at::empty({P, C}, x.options().dtype(kF));
+    db_part = part_rows();
     db = grad_out(db_out, C, x, &mask, 1);
   }
   at::Tensor dbb_part, dbb;
   if (has_bb) {
-    dbb_part = at::empty({P, C}, x.options().dtype(kF));
+    dbb_part = part_rows();
     dbb = grad_out(dbb_out, C, x, &mask, 2);
   }
   vcx_ln_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
              opt_ptr(dres), dx.data_ptr(), dw_part.data_ptr<float>(), has_bias ? db_part.data_ptr<float>() : nullptr,
              dw.data_ptr(), has_bias ? db.data_ptr() : nullptr, (int)R, C, rms ? 1 : 0,
              has_bb ? dbb_part.data_ptr<float>() : nullptr, has_bb ? dbb.data_ptr() : nullptr,
-             at::empty({3 * VCX_COLSUM_NB * C}, x.options().dtype(kF)).data_ptr<float>(), mask, cur_stream());
+             defer ? nullptr : at::empty({3 * VCX_COLSUM_NB * C}, x.options().dtype(kF)).data_ptr<float>(), mask,
+             defer ? 1 : 0, cur_stream());
   return {dx, dw, db, dbb};
+}
+
+// out[C] (+)= column sums of the fp32 partial rows part[P, C] (the two-stage finish on its own)
+at::Tensor colsum_f32(at::Tensor part, c10::optional<at::Tensor> out) {
+  CHECK_IN(part, kF);
+  TORCH_CHECK(part.dim() == 2 && part.size(0) < INT32_MAX && part.size(1) > 0 && part.size(1) < INT32_MAX,
+              "colsum_f32: part [P, C] fp32");
+  const int64_t P = part.size(0), C = part.size(1);
+  int mask = 0;
+  at::Tensor o = out ? grad_out(out, C, part, &mask, 0) : at::empty({C}, part.options().dtype(kBF));
+  auto stage = at::empty({VCX_COLSUM_NB * C}, part.options());
+  vcx_colsum_f32(part.data_ptr<float>(), o.data_ptr(), (int)P, (int)C, mask, stage.data_ptr<float>(), cur_stream());
+  return o;
+}
+
+// fp32 elements of the stage buffer colsum_finish_many needs for jobs of these widths
+int64_t colsum_finish_stage_floats(std::vector<int64_t> widths) {
+  std::vector<vcx::ColsumJob> jobs(widths.size());
+  for (size_t i = 0; i < widths.size(); ++i) {
+    TORCH_CHECK(widths[i] >= 0 && widths[i] < INT32_MAX, "colsum_finish_stage_floats: width");
+    jobs[i] = vcx::ColsumJob{};
+    jobs[i].C = (int)widths[i];
+  }
+  return vcx::colsum_stage_floats_max(jobs.data(), (int)jobs.size());
+}
+
+// outs[i] (bf16 [C_i]) (+)= column sums of parts[i] (fp32 [P_i, C_i], or [C_i] for one row), every job in one
+// stage-1 and one stage-2 launch per JOB_TABLE_CAP jobs, bit-identical to colsum_f32 per job. zero_src[i]:
+// parts[i] is left all-zero. stage: fp32, at least colsum_finish_stage_floats(widths). Returns the launches.
+int64_t colsum_finish_many(std::vector<at::Tensor> parts, std::vector<at::Tensor> outs, std::vector<bool> accumulate,
+                           std::vector<bool> zero_src, at::Tensor stage) {
+  const size_t n = parts.size();
+  TORCH_CHECK(outs.size() == n && accumulate.size() == n && zero_src.size() == n,
+              "colsum_finish_many: one out, accumulate and zero_src per part");
+  if (n == 0) return 0;
+  CHECK_IN(stage, kF);
+  std::vector<vcx::ColsumJob> jobs(n);
+  for (size_t i = 0; i < n; ++i) {
+    const at::Tensor& p = parts[i];
+    const at::Tensor& o = outs[i];
+    CHECK_IN(p, kF);
+    CHECK_IN(o, kBF);
+    const int64_t C = o.numel();
+    TORCH_CHECK((p.dim() == 1 || p.dim() == 2) && p.size(-1) == C && C < INT32_MAX && p.numel() / (C ? C : 1) < INT32_MAX &&
+                    p.get_device() == stage.get_device() && o.get_device() == stage.get_device(),
+                "colsum_finish_many: part [P, C] fp32 and out [C] bf16 on the stage's device");
+    vcx::ColsumJob j{};
+    j.part = p.data_ptr<float>();
+    j.P = C ? (int)(p.numel() / C) : 0;
+    j.C = (int)C;
+    j.out = o.data_ptr();
+    j.accumulate = accumulate[i] ? 1 : 0;
+    j.zero_src = zero_src[i] ? 1 : 0;
+    jobs[i] = j;
+  }
+  TORCH_CHECK(stage.numel() >= vcx::colsum_stage_floats_max(jobs.data(), (int)n), "colsum_finish_many: stage too small");
+  const int launches = vcx_colsum_finish_many(jobs.data(), (int)n, stage.data_ptr<float>(), stage.numel(), cur_stream());
+  TORCH_CHECK(launches >= 0, "colsum_finish_many: a job the table does not take");
+  return launches;
 }
 
 // out[F] (+)= column sums of y [.., F] (bias gradient of a token-major GEMM output)
@@ -1038,7 +1109,7 @@ at::Tensor attn_bwd(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor 
 // bias), reduced from per-block column sums the backward kernels emit — no separate pass over
 // dqkv. db_out: the preset (flat) gradient buffer to add into; returned otherwise.
 std::vector<at::Tensor> attn_bwd_bias(at::Tensor qkv, at::Tensor out, at::Tensor dout, at::Tensor lse, double scale,
-                                      c10::optional<at::Tensor> db_out) {
+                                      c10::optional<at::Tensor> db_out, c10::optional<at::Tensor> part_in, bool defer) {
   CHECK_IN(qkv, kBF);
   CHECK_IN(out, kBF);
   CHECK_IN(dout, kBF);
@@ -1050,13 +1121,22 @@ std::vector<at::Tensor> attn_bwd_bias(at::Tensor qkv, at::Tensor out, at::Tensor
   auto dqkv = at::empty_like(qkv);
   auto delta = at::empty({B, H, T}, lse.options());
   const int P = vcx_attn_bias_partials((int)B, (int)T);
-  auto part = at::empty({P, F}, lse.options());
+  // part_in: the caller's [P, F] fp32 partial rows; defer: they are left unreduced for colsum_finish_many
+  if (part_in) {
+    CHECK_IN((*part_in), kF);
+    TORCH_CHECK(part_in->dim() == 2 && part_in->size(0) == P && part_in->size(1) == F,
+                "attn_bwd_bias: part must be [attn_bias_partials(B, T), 3 * H * 64] fp32");
+  }
+  TORCH_CHECK(!defer || part_in, "attn_bwd_bias: defer needs the caller's part");
+  auto part = part_in ? *part_in : at::empty({P, F}, lse.options());
   int mask = 0;
   at::Tensor db = grad_out(db_out, F, qkv, &mask, 0);
-  auto stage = at::empty({VCX_COLSUM_NB * F}, lse.options());
   vcx_attn_bwd_d64(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr<float>(), delta.data_ptr<float>(),
                    dqkv.data_ptr(), part.data_ptr<float>(), (int)B, (int)T, (int)H, (float)scale, cur_stream());
-  vcx_colsum_f32(part.data_ptr<float>(), db.data_ptr(), P, (int)F, mask, stage.data_ptr<float>(), cur_stream());
+  if (!defer) {
+    auto stage = at::empty({VCX_COLSUM_NB * F}, lse.options());
+    vcx_colsum_f32(part.data_ptr<float>(), db.data_ptr(), P, (int)F, mask, stage.data_ptr<float>(), cur_stream());
+  }
   return {dqkv, db};
 }
 
@@ -1167,7 +1247,15 @@ PYBIND11_MODULE(_C, m) {
   m.def("ln_bwd", &ln_bwd, pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("mean"),
         pybind11::arg("rstd"), pybind11::arg("dres"), pybind11::arg("has_bias"), pybind11::arg("rms"),
         pybind11::arg("has_bb"), pybind11::arg("dw_out") = pybind11::none(), pybind11::arg("db_out") = pybind11::none(),
-        pybind11::arg("dbb_out") = pybind11::none());
+        pybind11::arg("dbb_out") = pybind11::none(), pybind11::arg("parts") = pybind11::none(),
+        pybind11::arg("defer") = false);
+  m.def("ln_bwd_partials", [](int64_t R, int64_t C) { return (int64_t)vcx_ln_bwd_partials((int)R, (int)C); });
+  m.def("attn_bias_partials", [](int64_t B, int64_t T) { return (int64_t)vcx_attn_bias_partials((int)B, (int)T); });
+  m.attr("COLSUM_NB") = (int64_t)VCX_COLSUM_NB;
+  m.def("colsum_f32", &colsum_f32, pybind11::arg("part"), pybind11::arg("out") = pybind11::none());
+  m.def("colsum_finish_stage_floats", &colsum_finish_stage_floats, pybind11::arg("widths"));
+  m.def("colsum_finish_many", &colsum_finish_many, pybind11::arg("parts"), pybind11::arg("outs"),
+        pybind11::arg("accumulate"), pybind11::arg("zero_src"), pybind11::arg("stage"));
   m.def("colsum_bf16", &colsum_bf16, pybind11::arg("y"), pybind11::arg("out") = pybind11::none());
   m.def("gelu_fwd", &gelu_fwd);
   m.def("bias_gelu_fwd", &bias_gelu_fwd);
@@ -1193,7 +1281,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("attn_hm_bwd", &attn_hm_bwd);
   m.def("attn_hm_set_variant", &vcx_attn_hm_set_variant);
   m.def("attn_bwd_bias", &attn_bwd_bias, pybind11::arg("qkv"), pybind11::arg("out"), pybind11::arg("dout"),
-        pybind11::arg("lse"), pybind11::arg("scale"), pybind11::arg("db_out") = pybind11::none());
+        pybind11::arg("lse"), pybind11::arg("scale"), pybind11::arg("db_out") = pybind11::none(),
+        pybind11::arg("part") = pybind11::none(), pybind11::arg("defer") = false);
   vcx_register_vision(m);
   vcx_register_compress(m);
   vcx_register_lt(m);

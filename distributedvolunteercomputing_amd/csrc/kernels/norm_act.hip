@@ -503,15 +503,17 @@ __global__ void __launch_bounds__(TPB) colsum_part_bf16_kernel(const bf16* __res
 // launches for all outputs together. Stage 1: grid (C/64, NB, nout) -- every block reduces
 // P/NB rows of 64 columns (4 waves, LDS combine) into stage[out][NB][C]; stage 2: NB rows -> bf16.
 // (A single-stage sum had only C/64 blocks -- 12 for C = 768 -- and ran latency-bound.)
-__global__ void __launch_bounds__(256) colsum_stage1_kernel(const float* __restrict__ p0, const float* __restrict__ p1,
-                                                            const float* __restrict__ p2, float* __restrict__ stage,
-                                                            int P, int C) {
-  __shared__ float red[4][64];
+// The two bodies are shared with the many-job kernels below, so both forms add the same terms in the same order.
+// Stage 1 of one workgroup: rows [r0, r1) of chunk `by` of 64 columns of part[P, C] into stage_row[c] (the
+// row of this output / job and chunk). ZERO: every element read is left zeroed; each element of part is read by
+// exactly one thread of the grid, so no other reader can see the zero.
+template <bool ZERO>
+__device__ __forceinline__ void colsum_stage1_body(const float* __restrict__ part, float* __restrict__ stage_row,
+                                                   int P, int C, int by, int NB, float (*red)[64]) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int out = blockIdx.z, NB = gridDim.y, by = blockIdx.y;
-  const float* part = out == 0 ? p0 : (out == 1 ? p1 : p2);
   const int c = blockIdx.x * 64 + lane;
-  const int r0 = (int)((int64_t)P * by / NB), r1 = (int)((int64_t)P * (by + 1) / NB);
+  int r0, r1;
+  colsum_rows(P, by, NB, &r0, &r1);
   float acc = 0.f;
   if (c < C) {
     int r = r0 + w;
@@ -519,12 +521,46 @@ __global__ void __launch_bounds__(256) colsum_stage1_kernel(const float* __restr
       const float a0 = part[(int64_t)r * C + c], a1 = part[(int64_t)(r + 4) * C + c];
       const float a2 = part[(int64_t)(r + 8) * C + c], a3 = part[(int64_t)(r + 12) * C + c];
       acc += (a0 + a1) + (a2 + a3);
+      if (ZERO) {
+        float* z = const_cast<float*>(part);
+        z[(int64_t)r * C + c] = 0.f;
+        z[(int64_t)(r + 4) * C + c] = 0.f;
+        z[(int64_t)(r + 8) * C + c] = 0.f;
+        z[(int64_t)(r + 12) * C + c] = 0.f;
+      }
     }
-    for (; r < r1; r += 4) acc += part[(int64_t)r * C + c];
+    for (; r < r1; r += 4) {
+      acc += part[(int64_t)r * C + c];
+      if (ZERO) const_cast<float*>(part)[(int64_t)r * C + c] = 0.f;
+    }
   }
   red[w][lane] = acc;
   __syncthreads();
-  if (w == 0 && c < C) stage[((int64_t)out * NB + by) * C + c] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+  if (w == 0 && c < C) stage_row[c] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+}
+
+// Stage 2 of one thread: column c of the NB stage rows at st, st + stride, ... -> o[c] (bf16)
+__device__ __forceinline__ void colsum_stage2_body(const float* __restrict__ st, int64_t stride, bf16* __restrict__ o,
+                                                   int c, int accumulate) {
+  // NB is always VCX_COLSUM_NB: fully unrolled so all loads are in flight at once instead of a
+  // chain of dependent L2 round trips
+  float v[VCX_COLSUM_NB];
+#pragma unroll
+  for (int i = 0; i < VCX_COLSUM_NB; ++i) v[i] = st[(int64_t)i * stride];
+  float acc = 0.f;
+#pragma unroll
+  for (int i = 0; i < VCX_COLSUM_NB; ++i) acc += v[i];
+  if (accumulate) acc += (float)o[c];  // add into an existing (flat) gradient
+  o[c] = (bf16)acc;
+}
+
+__global__ void __launch_bounds__(256) colsum_stage1_kernel(const float* __restrict__ p0, const float* __restrict__ p1,
+                                                            const float* __restrict__ p2, float* __restrict__ stage,
+                                                            int P, int C) {
+  __shared__ float red[4][64];
+  const int out = blockIdx.z, NB = gridDim.y, by = blockIdx.y;
+  const float* part = out == 0 ? p0 : (out == 1 ? p1 : p2);
+  colsum_stage1_body<false>(part, stage + colsum_stage_row(out, by, NB, C), P, C, by, NB, red);
 }
 
 __global__ void __launch_bounds__(64) colsum_stage2_kernel(const float* __restrict__ stage, int NB, int C,
@@ -533,18 +569,32 @@ __global__ void __launch_bounds__(64) colsum_stage2_kernel(const float* __restri
   const int out = blockIdx.y;
   const int c = blockIdx.x * 64 + threadIdx.x;
   if (c >= C) return;
-  const float* st = stage + (int64_t)out * NB * C + c;
-  // NB is always VCX_COLSUM_NB: fully unrolled so all loads are in flight at once instead of a
-  // chain of dependent L2 round trips
-  float v[VCX_COLSUM_NB];
-#pragma unroll
-  for (int i = 0; i < VCX_COLSUM_NB; ++i) v[i] = st[(int64_t)i * C];
-  float acc = 0.f;
-#pragma unroll
-  for (int i = 0; i < VCX_COLSUM_NB; ++i) acc += v[i];
   bf16* o = out == 0 ? o0 : (out == 1 ? o1 : o2);
-  if ((accum_mask >> out) & 1) acc += (float)o[c];  // add into an existing (flat) gradient
-  o[c] = (bf16)acc;
+  colsum_stage2_body(stage + colsum_stage_row(out, 0, NB, C) + c, C, o, c, (accum_mask >> out) & 1);
+}
+
+// The same two stages for every job of a table (colsum_table.h) in one launch each: blockIdx.z (stage 1) /
+// blockIdx.y (stage 2) is the job, the stage buffer is [njobs][NB][Cmax]. The early return is uniform per
+// workgroup, so the body's barrier is reached by all threads of every workgroup that enters it.
+__global__ void __launch_bounds__(256) colsum_stage1_many_kernel(const ColsumTable tab, float* __restrict__ stage) {
+  __shared__ float red[4][64];
+  const int j = blockIdx.z, by = blockIdx.y;
+  const int C = tab.job[j].C;
+  if ((int)blockIdx.x * 64 >= C) return;
+  float* row = stage + colsum_stage_row(j, by, VCX_COLSUM_NB, tab.Cmax);
+  if (tab.job[j].zero_src)
+    colsum_stage1_body<true>(tab.job[j].part, row, tab.job[j].P, C, by, VCX_COLSUM_NB, red);
+  else
+    colsum_stage1_body<false>(tab.job[j].part, row, tab.job[j].P, C, by, VCX_COLSUM_NB, red);
+}
+
+__global__ void __launch_bounds__(64) colsum_stage2_many_kernel(const ColsumTable tab,
+                                                                const float* __restrict__ stage) {
+  const int j = blockIdx.y;
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= tab.job[j].C) return;
+  colsum_stage2_body(stage + colsum_stage_row(j, 0, VCX_COLSUM_NB, tab.Cmax) + c, tab.Cmax, (bf16*)tab.job[j].out, c,
+                     tab.job[j].accumulate);
 }
 
 // ============================================================ tanh-GELU
@@ -935,7 +985,7 @@ int vcx_ln_bwd_partials(int R, int C) {
 
 void vcx_ln_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd, const void* dres,
                 void* dx, float* dw_part, float* db_part, void* dw, void* db, int R, int C, int rms, float* dbb_part,
-                void* dbb, float* stage, int accum_mask, hipStream_t s) {
+                void* dbb, float* stage, int accum_mask, int defer, hipStream_t s) {
   const int ch = (C / 8 + 63) / 64;
   const int P = vcx_ln_bwd_partials(R, C);
   dim3 grid(ln_bwd_blocks(R, C));
@@ -957,6 +1007,7 @@ void vcx_ln_bwd(const void* dy, const void* x, const void* w, const float* mean,
                                            (const bf16*)x, (const bf16*)w, mean, rstd, (const bf16*)nullptr,
                                            (bf16*)dx, dw_part, db_part, R, C, rms, dbb_part));
   }
+  if (defer) return;  // the caller finishes the partials later (vcx_colsum_finish_many)
   // dw, then db and dbb when present, in one pair of launches; accum_mask bit 0/1/2 = add dw/db/dbb
   // into the existing output (a view of the flat gradient buffer) instead of overwriting it
   const float* ps[3] = {dw_part, nullptr, nullptr};
@@ -978,6 +1029,21 @@ void vcx_ln_bwd(const void* dy, const void* x, const void* w, const float* mean,
 
 void vcx_colsum_f32(const float* part, void* out, int P, int C, int accumulate, float* stage, hipStream_t s) {
   colsums(part, nullptr, nullptr, out, nullptr, nullptr, 1, P, C, stage, s, accumulate ? 1 : 0);
+}
+
+int vcx_colsum_finish_many(const vcx::ColsumJob* jobs, int n, float* stage, int64_t stage_floats, hipStream_t s) {
+  int launches = 0;
+  for (int i = 0; i < n;) {
+    ColsumTable tab{};
+    i = pack_colsum_jobs(jobs, n, i, &tab);
+    if (i < 0 || colsum_stage_floats(tab) > stage_floats) return -1;
+    if (tab.njobs == 0) break;  // only jobs without columns were left
+    const int gx = colsum_grid_x(tab);
+    hipLaunchKernelGGL(colsum_stage1_many_kernel, dim3(gx, VCX_COLSUM_NB, tab.njobs), dim3(256), 0, s, tab, stage);
+    hipLaunchKernelGGL(colsum_stage2_many_kernel, dim3(gx, tab.njobs), dim3(64), 0, s, tab, (const float*)stage);
+    launches += 2;
+  }
+  return launches;
 }
 
 void vcx_colsum_bf16(const void* y, float* part, void* out, int R, int F, int accumulate, float* stage,

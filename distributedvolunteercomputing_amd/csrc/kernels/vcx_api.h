@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "colsum_table.h"
 #include "job_table.h"
 
 // optim.hip
@@ -83,7 +84,7 @@ void vcx_ln_fwd(const void* a, const void* b, void* xout, void* y, const void* w
                 float* rstd, int R, int C, float eps, int rms, const void* bb, hipStream_t s);
 int vcx_bias_gelu_partials(int R);
 void vcx_bias_gelu_fwd(const void* x, const void* b, void* y, int R, int F, hipStream_t s);
-constexpr int VCX_COLSUM_NB = 32;  // stage-1 row chunks of the two-stage column sums (stage: 3 * NB * C fp32)
+constexpr int VCX_COLSUM_NB = vcx::COLSUM_NB;  // stage-1 row chunks of the two-stage column sums (stage: 3 * NB * C fp32)
 void vcx_bias_gelu_bwd(const void* x, const void* b, const void* dy, void* dx, float* part, void* db, int R, int F,
                        float* stage, int accumulate, hipStream_t s);
 // column sums of a bf16 [R, F] matrix into out[F] (bf16; added to it when accumulate != 0)
@@ -94,7 +95,11 @@ void vcx_colsum_bf16(const void* y, float* part, void* out, int R, int F, int ac
 int vcx_ln_bwd_partials(int R, int C);
 void vcx_ln_bwd(const void* dy, const void* x, const void* w, const float* mean, const float* rstd, const void* dres,
                 void* dx, float* dw_part, float* db_part, void* dw, void* db, int R, int C, int rms, float* dbb_part,
-                void* dbb, float* stage, int accum_mask, hipStream_t s);
+                void* dbb, float* stage, int accum_mask, int defer, hipStream_t s);
+// every job of jobs[0..n) finished as vcx_colsum_f32 would (bit-identical sums), in one stage-1 and one stage-2
+// launch per JOBS_MAX jobs (colsum_table.h); stage: colsum_stage_floats_max(jobs, n) fp32. Returns the launches
+// made, or -1 (possibly after earlier tables were launched) for a job the packer refuses or a stage too small
+int vcx_colsum_finish_many(const vcx::ColsumJob* jobs, int n, float* stage, int64_t stage_floats, hipStream_t s);
 void vcx_gelu_fwd(const void* x, void* y, int64_t n, hipStream_t s);
 void vcx_gelu_bwd(const void* x, const void* dy, void* dx, int64_t n, hipStream_t s);
 void vcx_swiglu_fwd(const void* gu, void* y, int64_t R, int F, hipStream_t s);

@@ -1,6 +1,7 @@
 """Hot ops. On GPU every op here runs a hand-written gfx950 HIP kernel from ``_C``;
 on CPU the same call runs the plain-PyTorch reference (used by tests and CPU volunteers)."""
 from ._lib import available as native_available, native  # noqa: F401
+from ._deferred import ColsumPool, deferred_colsums  # noqa: F401
 from .activations import bias_gelu, gelu, swiglu  # noqa: F401
 from .attention import causal_attention, fused_bias_grad_ok, gqa_attention  # noqa: F401
 from .embedding import embed  # noqa: F401

@@ -12,6 +12,7 @@ import math
 import torch
 import torch.nn.functional as F
 
+from . import _deferred
 from ._lib import grad_buffer, native, use_native
 
 
@@ -35,6 +36,14 @@ class _Attn(torch.autograd.Function):
         # the backward kernels also emit per-block column sums of dqkv = the gradient of the bias
         # the QKV projection added (linear(..., bias_grad_elsewhere=True)): no pass over dqkv
         gb = grad_buffer(bias)
+        pool = _deferred.active()
+        if pool is not None and gb is not None:
+            # the per-block sums stay in the pool's persistent buffer; finished with the pass's other column sums
+            B, T = qkv.shape[0], qkv.shape[1]
+            part = pool.partials((C.attn_bias_partials(B, T), bias.numel()), qkv.device)
+            dqkv = C.attn_bwd_bias(qkv, out, dout.contiguous(), lse, ctx.scale, gb, part, True)[0]
+            pool.register(part, gb.view(-1), accumulate=True)
+            return dqkv, None, None
         dqkv, db = C.attn_bwd_bias(qkv, out, dout.contiguous(), lse, ctx.scale, gb)
         return dqkv, None, (None if gb is not None else db.view_as(bias))
 

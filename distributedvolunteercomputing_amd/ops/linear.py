@@ -30,6 +30,7 @@ import torch.nn.functional as F
 
 
 from .. import config
+from . import _deferred
 from ._lib import grad_buffer, native, use_native
 
 MIN_ROWS_PER_SPLIT = 2048
@@ -459,7 +460,7 @@ class _Linear(torch.autograd.Function):
                 dx = gemm_f(dy2, transpose_weight(w) if wt is None else wt).view(x.shape)
             elif narrow_gemm_ok(dy2.shape[0], K, N, dy2):
                 dx = narrow_gemm(dy2, transpose_weight(w) if wt is None else wt).view(x.shape)
-            elif dgrad_ps_ok(dy2.shape[0], K, N, dy2):
+            elif dgrad_ps_ok(dy2.shape[0], K, N, dy2) and not (wt is not None and config.get().dgrad_nt_attn):
                 # dX = dY W on the persistent hand-written GEMM (B = W^T, a few MB): faster than the
                 # library at the GPT-2 attention shapes (profiles/r4_gemm_ps_bench.txt: dg_qkv, dg_proj)
                 dx = torch.empty(dy2.shape[0], K, device=dy2.device, dtype=dy2.dtype)
@@ -519,7 +520,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = None,
 # ---------------------------------------------------------------- fused GPT-2 MLP
 def dgrad_ps_ok(M: int, N: int, K: int, t) -> bool:
     """Input gradient dX[M, N] = dY[M, K] W[K, N] on gemm_ps: where it measured faster than the
-    library (K <= 2304: the qkv and attention-output projections; at K = 3072 it is 3 % slower)."""
+    library (K <= 2304: the qkv and attention-output projections; at K = 3072 it is 3 % slower). A layer that was
+    handed W^T takes the NT library GEMM on it instead while config.dgrad_nt_attn is on (``_Linear.backward``)."""
     return (config.get().dgrad_ps and K <= 2304 and use_native(t) and t.dtype == torch.bfloat16
             and t.is_contiguous() and bool(native().gemm_ps_supported(M, N, K, 0)))
 
@@ -570,7 +572,13 @@ class _MlpGelu(torch.autograd.Function):
         gb = grad_buffer(b1) if ctx.needs_input_grad[2] else None
         # the bias gradient's fp32 column sums: a zero-at-rest buffer per (size, device, stream) that the add into
         # the flat .grad zeroes again (no fill launch per layer), a fresh zero tensor when the sums are returned
-        cs = _colsum_buffer(F_, dy.device) if gb is not None else torch.zeros(F_, device=dy.device, dtype=torch.float32)
+        pool = _deferred.active() if gb is not None else None
+        if pool is not None:
+            # deferred: this layer's own zero-at-rest row (the shared one would mix the layers' sums); its add into
+            # the flat .grad is a one-row zero_src job of the pass's column-sum finish
+            cs = pool.partials((F_,), dy.device, zero=True)
+        else:
+            cs = _colsum_buffer(F_, dy.device) if gb is not None else torch.zeros(F_, device=dy.device, dtype=torch.float32)
         dpre = torch.empty_like(pre)
         w1t = ctx.w1t
         w2t = transpose_weight(w2) if ctx.w2t is None else ctx.w2t
@@ -582,7 +590,9 @@ class _MlpGelu(torch.autograd.Function):
         dw1, _ = _param_grads(dpre, x2, w1, None, ctx.needs_input_grad[1], False)
         db1 = None
         if ctx.needs_input_grad[2]:
-            if gb is not None:
+            if pool is not None:
+                pool.register(cs, gb, accumulate=True, zero_src=True)
+            elif gb is not None:
                 C.add_f32_into_bf16(cs, gb, True, True)
             else:
                 db1 = cs.to(b1.dtype)

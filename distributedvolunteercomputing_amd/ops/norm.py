@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import torch
 
+from . import _deferred
 from ._lib import grad_buffer, native, use_native
 
 
@@ -60,6 +61,18 @@ class _AddLN(torch.autograd.Function):
         dres = None if dx_res is None else dx_res.contiguous()
         pw, pbias, pbb = ctx.params
         gw, gb, gbb = grad_buffer(pw), grad_buffer(pbias) if ctx.has_bias else None, grad_buffer(pbb) if ctx.has_bb else None
+        pool = _deferred.active()
+        if pool is not None and gw is not None and (gb is not None) == ctx.has_bias and (gbb is not None) == ctx.has_bb:
+            # every column sum goes into the flat gradient: the kernel leaves its partial rows in the pool's
+            # persistent buffer and the sums are finished with every other job of this backward pass
+            outs = [g for g in (gw, gb, gbb) if g is not None]
+            Cw = x.shape[-1]
+            parts = pool.partials((len(outs), C.ln_bwd_partials(x.numel() // Cw, Cw), Cw), x.device)
+            dx = C.ln_bwd(dy.contiguous(), x, w, mean, rstd, dres, ctx.has_bias, ctx.rms, ctx.has_bb, gw, gb, gbb,
+                          parts, True)[0]
+            for k, g in enumerate(outs):
+                pool.register(parts[k], g, accumulate=True)
+            return dx, (dx if ctx.has_b else None), None, None, None, None, None
         dx, dw, dbias, dbb = C.ln_bwd(dy.contiguous(), x, w, mean, rstd, dres, ctx.has_bias, ctx.rms, ctx.has_bb,
                                       gw, gb, gbb)
         # parameter gradients already added into preset buffers are not handed to autograd again

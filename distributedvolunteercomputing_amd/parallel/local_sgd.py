@@ -133,6 +133,9 @@ class LocalSGDTrainer:
         self.delta = torch.zeros(n, dtype=cfg.comm_dtype, device=self.device)
         self.outer_mom = torch.zeros(n, dtype=torch.float32, device=self.device) if cfg.outer_momentum > 0 else None
         self.ostate = ops.new_ostate(self.device, cfg.lr)
+        # persistent partial buffers of the deferred column sums: never freed while the trainer lives (a captured
+        # step keeps their addresses)
+        self._colsums = ops.ColsumPool()
         self.membership = membership
         self.group = membership.group if membership is not None else group
         self.compressor = compressor
@@ -156,7 +159,10 @@ class LocalSGDTrainer:
     def forward_backward(self, x, y):
         self.flat.zero_grad()
         loss = self.model(x, y)
-        loss.backward()
+        # the bias / LayerNorm column sums of every layer are finished together on leaving the scope, before
+        # grad_sumsq / clip / AdamW read the gradient (eager and captured step alike: capture() records this)
+        with ops.deferred_colsums(self._colsums):
+            loss.backward()
         return loss
 
     def optimizer_step(self):

@@ -68,9 +68,7 @@ class RuntimeConfig:
     # ResNet-50 stage 2's [128, 256 | 512]) on gemm_wg too -- config 3 8849-8871 vs 8918-8960 img/s without
     # (gpurun_out/c26), so off; the LM heads take the ragged panel regardless
     wgrad_ragged: bool = False
-    gemm_select: bool = False  # VCX_GEMM_SELECT: per-shape layout probe of the forward GEMMs (no in-step gain)
     wgrad_big_split_min_m: int = 16384  # VCX_WGRAD_BIG_SPLIT_MIN_M: rows above which weight grads split over K
-    async_wgrad: bool = False  # VCX_ASYNC_WGRAD: weight-grad GEMMs on a side stream (measured slower)
     lmhead_chunk: int = 0  # VCX_LMHEAD_CHUNK: token rows per LM-head GEMM + xent pass (0 = one pass)
     force_reference_ops: bool = False  # VCX_FORCE_REFERENCE_OPS: torch ops instead of the HIP kernels
     tunableop: str = "on"  # VCX_TUNABLEOP: "on" loads the shipped hipBLASLt selections, "off" skips them
@@ -157,9 +155,7 @@ _ENV = {
     "gemm_fwd": ("VCX_GEMM_FWD", str),
     "wgrad_wide": ("VCX_WGRAD_WIDE", _bool),
     "wgrad_ragged": ("VCX_WGRAD_RAGGED", _bool),
-    "gemm_select": ("VCX_GEMM_SELECT", _bool),
     "wgrad_big_split_min_m": ("VCX_WGRAD_BIG_SPLIT_MIN_M", int),
-    "async_wgrad": ("VCX_ASYNC_WGRAD", _bool),
     "lmhead_chunk": ("VCX_LMHEAD_CHUNK", int),
     "force_reference_ops": ("VCX_FORCE_REFERENCE_OPS", _bool),
     "tunableop": ("VCX_TUNABLEOP", str),

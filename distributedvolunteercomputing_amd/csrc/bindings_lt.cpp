@@ -1,7 +1,7 @@
 // hipBLASLt GEMMs with an in-process per-shape algorithm search and optional epilogues (gfx950).
 //
-// Used by ops/linear.py's per-shape library selection (VCX_GEMM_SELECT=1) and by the probes in
-// scripts/. Measured on this image's hipBLASLt (scripts/lt_probe3.py): BIAS / GELU / GELU_BIAS /
+// Used by the probes in scripts/ (ops/linear.py's per-shape library selection, which also called it, showed no
+// in-step gain and was removed). Measured on this image's hipBLASLt (scripts/lt_probe3.py): BIAS / GELU / GELU_BIAS /
 // DGELU have bf16 algorithms at the GPT-2 MLP shapes, GELU_AUX(_BIAS) / DGELU_BGRAD / BGRADB do
 // not, and DGELU does not compute the tanh-GELU derivative the model needs — so the MLP keeps its
 // GEMM + HIP bias-GELU kernels, and the selection layer stays opt-in (A/B: no in-step gain).

@@ -18,7 +18,7 @@ import torch.nn.functional as F
 
 from .. import config
 from ..ops.batchnorm import bn_act, global_avgpool, stem_maxpool
-from ..ops.linear import GradJoin, residual_tap
+from ..ops.grad_join import GradJoin, residual_tap, subsample_tap
 
 
 class Conv1x1(nn.Conv2d):
@@ -40,11 +40,11 @@ class Conv1x1(nn.Conv2d):
                 and x.is_contiguous(memory_format=torch.channels_last)):
             assert join is None
             return super().forward(x)
-        from ..ops.linear import linear, subsample_tap
+        from ..ops.linear import linear
 
         if self.stride[0] != 1:
             assert not deposit
-            if join is not None:  # the input gradient lands in the one conv1 deposited (ops/linear.py GradJoin)
+            if join is not None:  # the input gradient lands in the one conv1 deposited (ops/grad_join.py GradJoin)
                 xh, join = subsample_tap(x, join, self.stride[0]), None
             else:
                 xh = x.permute(0, 2, 3, 1)[:, ::self.stride[0], ::self.stride[1], :].contiguous()
@@ -182,7 +182,7 @@ class Bottleneck(nn.Module):
         # BatchNorm + ReLU (+ the residual add) as fused HIP passes in train mode (ops/batchnorm.py).
         # Identity shortcut: x feeds conv1 and the residual add, so autograd would sum the two
         # gradients of x in an elementwise pass; the shortcut's gradient goes to conv1's input-gradient
-        # GEMM instead, which adds it as its C (beta = 1; ops/linear.py GradJoin)
+        # GEMM instead, which adds it as its C (beta = 1; ops/grad_join.py GradJoin)
         # Projection shortcut: conv1's input gradient is left in the join and the shortcut convolution
         # (older node, so its backward runs later) adds its own into it -- beta = 1 at stride 1, a
         # strided in-place add at stride 2 -- instead of autograd's full-size zero fill + slice copy + add

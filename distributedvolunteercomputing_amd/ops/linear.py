@@ -18,20 +18,27 @@ W on W^T, 200 vs 207 us and 72 vs 77 us; ``dgrad_ps_ok``). The other forward GEM
 library, where gemm_ps measures 0.86-0.97x (its stores slow the next tile's main loop:
 profiles/r4_gemm_ps_diag.txt). ``VCX_GEMM=vcx`` switches the forward and input-gradient GEMMs to
 the older tiled ``gemm_nt`` (csrc/kernels/gemm.hip), slower at these shapes (profiles/r2_gemm_nt.txt).
-Other shapes go through ``mm``: per GEMM shape, the first call outside graph capture can time the
-TunableOp-selected library GEMM (hipBLASLt / rocBLAS, utils/tuning.py) against hipBLASLt with this
-process's own per-shape algorithm search (csrc/bindings_lt.cpp). The bias gradient is a HIP
-column-sum kernel added into the flat gradient buffer.
+Everything else goes through ``mm``, the TunableOp-selected library GEMM (hipBLASLt / rocBLAS,
+utils/tuning.py). The bias gradient is a HIP column-sum kernel added into the flat gradient buffer.
+
+Which GEMM runs is decided in one place: ``forward_route`` (Y = X W^T + b: nt | f | narrow | lib) and
+``dgrad_route`` (dX = dY W: the same three hand-written kernels on W^T, then ps | lib_nt | lib_nn), both
+over ``_gemm_route``, executed by ``_gemm``. ``linear_wants_wt`` is ``dgrad_route`` asked without a
+handle, and the fused MLP's GEMMs outside its two epilogue kernels are described by ``_mlp_routes``, which
+``_MlpGelu`` and ``mlp_wants_wt`` both read: the model makes W^T ahead of the backward exactly where the
+backward would otherwise make its own. The ``*_ok`` predicates carry the measurements behind each step of
+the chain.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn.functional as F
 
-
 from .. import config
 from . import _deferred
 from ._lib import grad_buffer, native, use_native
+# ``linear(..., join=)`` takes a GradJoin; the taps lived here before ops/grad_join.py and stay importable from here
+from .grad_join import GradJoin, residual_tap, subsample_tap  # noqa: F401
 
 MIN_ROWS_PER_SPLIT = 2048
 
@@ -112,79 +119,82 @@ def transpose_weights(ws, out=None):
     return native().transpose_bf16_many(ws, out)[0]
 
 
-def linear_wants_wt(M: int, w, t) -> bool:
-    """True when the backward of ``linear(x[M, K], w)`` reads W^T (``t``: the activations)."""
-    N, K = _w2(w).shape
-    return (gemm_nt_ok(M, K, N, t) or gemm_f_ok(M, K, N, t) or narrow_gemm_ok(M, K, N, t) or dgrad_ps_ok(M, K, N, t))
-
-
-def mlp_wants_wt(x, w1, w2):
-    """(fc, fc2): which of W1^T, W2^T the backward of ``mlp_gelu(x, w1, b1, w2)`` reads."""
-    mode = _mlp_mode(x, w1, w2)
-    if mode is None:
-        M = x.numel() // x.shape[-1]
-        return linear_wants_wt(M, w1, x), linear_wants_wt(M, w2, x)
-    return mode == "nt" or bool(config.get().fc_dgrad_nt), True
-
-
-_CHOICE: dict = {}  # (shapes, layout, bias) -> "torch" | "lt"
-
-
-def _torch_mm(a, b, trans_a, trans_b, bias):
+def mm(a, b, trans_a: bool = False, trans_b: bool = False, bias=None):
+    """op(a) @ op(b) (+ bias) on the library (a per-shape choice between it and an in-process hipBLASLt search
+    showed no in-step gain, 956 vs 957 samples/s, and was removed)."""
     if trans_b and not trans_a:  # x @ W^T (+ b): the F.linear / TunableOp GemmAndBias path
         return F.linear(a, b, bias)
     y = torch.mm(a.t() if trans_a else a, b.t() if trans_b else b)
     return y if bias is None else y.add_(bias)
 
 
-def _lt_mm(a, b, trans_a, trans_b, bias):
-    C = native()
-    M = a.shape[1] if trans_a else a.shape[0]
-    N = b.shape[0] if trans_b else b.shape[1]
-    out = torch.empty(M, N, device=a.device, dtype=a.dtype)
-    epi = C.LT_EPI_DEFAULT if bias is None else C.LT_EPI_BIAS
-    if not C.lt_matmul(a, b, out, trans_a, trans_b, epi, bias):
-        return None
-    return out
-
-
-def _time_ms(fn, reps=3):
-    fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def mm(a, b, trans_a: bool = False, trans_b: bool = False, bias=None):
-    """op(a) @ op(b) (+ bias) for 2-D bf16 GPU tensors, with per-shape library selection."""
-    # config.gemm_select; measured: no in-step gain (A/B 956 vs 957 samples/s)
-    if not (config.get().gemm_select and a.is_cuda and a.dtype == torch.bfloat16 and a.is_contiguous() and b.is_contiguous()):
-        return _torch_mm(a, b, trans_a, trans_b, bias)
-    key = (tuple(a.shape), tuple(b.shape), trans_a, trans_b, bias is not None)
-    c = _CHOICE.get(key)
-    if c is None:
-        if torch.cuda.is_current_stream_capturing():
-            return _torch_mm(a, b, trans_a, trans_b, bias)  # no timing inside a capture
-        t_torch = _time_ms(lambda: _torch_mm(a, b, trans_a, trans_b, bias))
-        c = "torch"
-        if _lt_mm(a, b, trans_a, trans_b, bias) is not None:  # runs hipBLASLt's own algorithm search
-            if _time_ms(lambda: _lt_mm(a, b, trans_a, trans_b, bias)) < 0.97 * t_torch:
-                c = "lt"
-        _CHOICE[key] = c
-    if c == "lt":
-        y = _lt_mm(a, b, trans_a, trans_b, bias)
-        if y is not None:
-            return y
-    return _torch_mm(a, b, trans_a, trans_b, bias)
-
-
 def gemm_choices() -> dict:
-    """{(a.shape, b.shape, trans_a, trans_b, bias): "torch" | "lt"} selected so far."""
-    return dict(_CHOICE)
+    return {}  # bench.py reports its size; the per-shape selection it listed is gone
+
+
+# ---------------------------------------------------------------- which GEMM runs
+def _gemm_route(M: int, N: int, K: int, t, bias=None):
+    """The hand-written kernel for out[M, N] = a[M, K] b[N, K]^T (+ bias): 'nt', 'f', 'narrow', or None."""
+    if gemm_nt_ok(M, N, K, t):
+        return "nt"
+    if gemm_f_ok(M, N, K, t) and (bias is None or bias.is_contiguous()):
+        return "f"
+    if bias is None and narrow_gemm_ok(M, N, K, t):
+        return "narrow"
+    return None
+
+
+def forward_route(M: int, N: int, K: int, t, bias=None) -> str:
+    """What computes Y[M, N] = X[M, K] W[N, K]^T (+ bias): 'nt' | 'f' | 'narrow' | 'lib' (``t``: the activations)."""
+    return _gemm_route(M, N, K, t, bias) or "lib"
+
+
+def dgrad_route(M: int, N: int, K: int, t, handle: bool) -> str:
+    """What computes dX[M, K] = dY[M, N] W[N, K] (``t``: dY; ``handle``: the layer was given W^T): 'nt' | 'f' |
+    'narrow' | 'ps' read W^T, and so does 'lib_nt'; 'lib_nn' reads W."""
+    route = _gemm_route(M, K, N, t)
+    if route is not None:
+        return route
+    if dgrad_ps_ok(M, K, N, t) and not (handle and config.get().dgrad_nt_attn):
+        # the persistent hand-written GEMM on B = W^T (a few MB): faster than the library at the GPT-2 attention
+        # shapes (profiles/r4_gemm_ps_bench.txt: dg_qkv, dg_proj)
+        return "ps"
+    # a handle and no hand-written kernel for the shape: dX = dY (W^T)^T as the NT library GEMM (the GPT-2-small LM
+    # head: 3.28 ms + 0.03 ms for wte^T against 3.83 ms for the NN form, profiles/bwd_helpers_step_kernels.txt); the
+    # caller decides by giving the handle
+    return "lib_nt" if handle else "lib_nn"
+
+
+def _gemm(route: str, a, b, bias=None):
+    """a[M, K] @ b[N, K]^T (+ bias) on the back-end a route names ('lib_nn' is not of this form)."""
+    if route == "nt":
+        return gemm_nt(a, b, bias)
+    if route == "f":
+        return gemm_f(a, b, bias)
+    if route == "narrow":
+        return narrow_gemm(a, b)
+    if route == "ps":
+        out = torch.empty(a.shape[0], b.shape[0], device=a.device, dtype=a.dtype)
+        native().gemm_ps(a, b, out)
+        return out
+    assert route in ("lib", "lib_nt"), route
+    return mm(a, b, trans_b=True, bias=bias)
+
+
+def linear_wants_wt(M: int, w, t) -> bool:
+    """True when the backward of ``linear(x[M, K], w)`` reads W^T (``t``: the activations)."""
+    N, K = _w2(w).shape
+    return dgrad_route(M, N, K, t, handle=False) != "lib_nn"
+
+
+def mlp_wants_wt(x, w1, w2):
+    """(fc, fc2): which of W1^T, W2^T the backward of ``mlp_gelu(x, w1, b1, w2)`` reads."""
+    mode = _mlp_mode(x, w1, w2)
+    M = x.numel() // x.shape[-1]
+    if mode is None:
+        return linear_wants_wt(M, w1, x), linear_wants_wt(M, w2, x)
+    # fc2's input gradient is the fused-epilogue GEMM on W2^T in either mode
+    return _mlp_routes(mode, M, w2.shape[0], w1.shape[0], x, handle=True)[1] != "lib_nn", True
 
 
 # Big outputs (N*K >= 16M elements) with fewer tokens than this take ONE GEMM that accumulates
@@ -256,43 +266,11 @@ def wgrad(dy2: torch.Tensor, x2: torch.Tensor, out: torch.Tensor | None = None, 
     return out
 
 
-# ---------------------------------------------------------------- side-stream weight gradients
-# The weight (and bias) gradient of a layer feeds nothing downstream in the backward pass — only
-# the optimizer after it. With VCX_ASYNC_WGRAD=1 (opt-in) those GEMMs + reductions are enqueued
-# on a side HIP stream (event fork from the main stream) and joined back once, at the end of the
-# backward pass (autograd engine callback), so the compute-bound split-M wgrad GEMMs run beside
-# the memory-bound kernels of the next layers' input-gradient chain (LayerNorm / GELU / attention
-# backward) instead of after them. Works under hipGraph capture (fork/join become graph edges).
-_SIDE: dict = {}
-_JOIN_PENDING: dict = {}
-
-
-def _side_stream(dev):
-    st = _SIDE.get(dev)
-    if st is None:
-        st = _SIDE[dev] = torch.cuda.Stream(device=dev)
-    return st
-
-
-def _queue_join(main, side, key):
-    """Make `main` wait for `side` when the running backward pass finishes (once per pass)."""
-    if _JOIN_PENDING.get(key):
-        return
-    _JOIN_PENDING[key] = True
-
-    def _join():
-        main.wait_stream(side)
-        _JOIN_PENDING[key] = False
-
-    torch.autograd.Variable._execution_engine.queue_callback(_join)
-
-
 def _param_grads(dy2, x2, w, bias, want_w, want_b):
     """(dw, db) to hand autograd: None where the gradient went into a preset flat .grad buffer."""
     dw = db = None
     N = w.shape[0]
-    g = w.grad if want_w else None
-    gw = g if g is not None and g.is_contiguous() and g.dtype == w.dtype and g.shape == w.shape else None
+    gw = grad_buffer(w) if want_w else None
     gb = grad_buffer(bias) if want_b else None
     if want_w:
         if gw is not None:
@@ -315,98 +293,6 @@ def _w2(w):
     return w if w.dim() == 2 else w.view(w.shape[0], -1)
 
 
-class GradJoin:
-    """Hands one extra gradient of a linear layer's input to that layer's backward, which adds it in
-    its input-gradient GEMM (beta = 1) instead of autograd adding the two gradients in a separate
-    elementwise pass. Made for a residual block whose input x feeds both its first 1x1 convolution
-    and the identity shortcut: ``residual_tap(x, join)`` on the shortcut passes its gradient here,
-    ``linear(x2d, w, join=join)`` adds it (models/resnet.py). Protocol (one backward pass at a
-    time, both sides on the autograd thread): the tap's backward runs first in practice (it becomes
-    ready at the block's last BatchNorm, the convolution only at the end of the branch); whichever
-    side runs second sees the other's state, so the result is right in either order.
-
-    Projection shortcuts run the other way round: the shortcut's nodes are older than conv1's, so
-    conv1's backward runs first and DEPOSITS its input gradient (``linear(..., join=j, deposit=True)``
-    returns None for x); the shortcut convolution then adds its own into that buffer -- with beta = 1
-    at stride 1, or as a strided in-place add at stride 2 (``subsample_tap``) instead of autograd's
-    zero-filled full-size slice gradient plus a full-size add."""
-
-    def __init__(self):
-        self.pending = None  # the shortcut's gradient as the [M, K] matrix of the layer input
-        self.ran = False     # the layer's backward ran without it (the tap then returns its gradient)
-
-    def take(self):
-        g, self.pending = self.pending, None
-        return g
-
-
-class _ResidualTap(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, join):
-        ctx.join = join
-        join.pending, join.ran = None, False
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        join, ctx.join = ctx.join, None
-        if join.ran or g.dim() != 4:
-            return g, None
-        gh = g.permute(0, 2, 3, 1)  # the [N, H, W, C] view the 1x1 convolution's GEMM uses
-        if not gh.is_contiguous():
-            return g, None
-        join.pending = gh.reshape(-1, gh.shape[-1])
-        return None, None
-
-
-def residual_tap(x: torch.Tensor, join: GradJoin) -> torch.Tensor:
-    """x itself (a view), whose gradient goes to ``join`` (channels-last 4-D x) instead of autograd."""
-    return _ResidualTap.apply(x, join)
-
-
-class _SubsampleTap(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, join, s):
-        ctx.join, ctx.s = join, s
-        ctx.full = (x.shape[0], x.shape[2], x.shape[3], x.shape[1])  # N, H, W, C
-        join.ran = False
-        xh = x.permute(0, 2, 3, 1)
-        ctx.hip = _nhwc_hip_ok(xh)
-        if ctx.hip:  # csrc/kernels/batchnorm.hip subsample_kernel: 16-B lanes (torch's strided copy: ~1.4 TB/s)
-            return native().subsample_nhwc(xh, s)
-        return xh[:, ::s, ::s, :].contiguous()
-
-    @staticmethod
-    def backward(ctx, g):
-        join, ctx.join = ctx.join, None
-        s, (N, H, W, C) = ctx.s, ctx.full
-        base = join.take()
-        if base is not None and base.is_contiguous() and base.numel() == N * H * W * C:
-            full = base.view(N, H, W, C)
-            # conv1's deposited input gradient: only the strided quarter moves
-            if ctx.hip and g.is_contiguous() and _nhwc_hip_ok(g) and full.dtype == g.dtype:
-                native().subsample_add_nhwc(full, g, s)
-            else:
-                full[:, ::s, ::s, :].add_(g)
-        else:
-            join.ran = True
-            full = g.new_zeros(N, H, W, C)
-            full[:, ::s, ::s, :] = g
-        return full.permute(0, 3, 1, 2), None, None
-
-
-def _nhwc_hip_ok(t: torch.Tensor) -> bool:
-    """A contiguous NHWC bf16 GPU tensor the strided-shortcut kernels take (C % 8 == 0, 16-B aligned)."""
-    return (use_native(t) and t.dtype == torch.bfloat16 and t.dim() == 4 and t.is_contiguous() and t.shape[3] % 8 == 0
-            and t.data_ptr() % 16 == 0)
-
-
-def subsample_tap(x: torch.Tensor, join: GradJoin, stride: int) -> torch.Tensor:
-    """The contiguous [N, H/s, W/s, C] subsample of channels-last 4-D x (a stride-s 1x1 convolution's
-    input); its backward adds the gradient into the input gradient conv1 deposited in ``join``."""
-    return _SubsampleTap.apply(x, join, stride)
-
-
 class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, bias_grad_elsewhere=False, join=None, deposit=False, wt=None):
@@ -423,13 +309,8 @@ class _Linear(torch.autograd.Function):
             join.pending, join.ran = None, False
         x2 = x.reshape(-1, x.shape[-1])
         w = _w2(w)
-        if gemm_nt_ok(x2.shape[0], w.shape[0], x2.shape[1], x2):
-            return gemm_nt(x2, w, b).view(*x.shape[:-1], w.shape[0])
-        if gemm_f_ok(x2.shape[0], w.shape[0], x2.shape[1], x2) and (b is None or b.is_contiguous()):
-            return gemm_f(x2, w, b).view(*x.shape[:-1], w.shape[0])
-        if b is None and narrow_gemm_ok(x2.shape[0], w.shape[0], x2.shape[1], x2):
-            return narrow_gemm(x2, w).view(*x.shape[:-1], w.shape[0])
-        return mm(x2, w, trans_b=True, bias=b).view(*x.shape[:-1], w.shape[0])
+        route = forward_route(x2.shape[0], w.shape[0], x2.shape[1], x2, b)
+        return _gemm(route, x2, w, b).view(*x.shape[:-1], w.shape[0])
 
     @staticmethod
     def backward(ctx, dy):
@@ -453,47 +334,18 @@ class _Linear(torch.autograd.Function):
         elif base is not None:
             dx = (mm(dy2, w) + base).view(x.shape) if ctx.needs_input_grad[0] else None
         elif ctx.needs_input_grad[0]:
-            wt = ctx.wt
-            if gemm_nt_ok(dy2.shape[0], K, N, dy2):
-                dx = gemm_nt(dy2, transpose_weight(w) if wt is None else wt).view(x.shape)
-            elif gemm_f_ok(dy2.shape[0], K, N, dy2):
-                dx = gemm_f(dy2, transpose_weight(w) if wt is None else wt).view(x.shape)
-            elif narrow_gemm_ok(dy2.shape[0], K, N, dy2):
-                dx = narrow_gemm(dy2, transpose_weight(w) if wt is None else wt).view(x.shape)
-            elif dgrad_ps_ok(dy2.shape[0], K, N, dy2) and not (wt is not None and config.get().dgrad_nt_attn):
-                # dX = dY W on the persistent hand-written GEMM (B = W^T, a few MB): faster than the
-                # library at the GPT-2 attention shapes (profiles/r4_gemm_ps_bench.txt: dg_qkv, dg_proj)
-                dx = torch.empty(dy2.shape[0], K, device=dy2.device, dtype=dy2.dtype)
-                native().gemm_ps(dy2, transpose_weight(w) if wt is None else wt, dx)
-                dx = dx.view(x.shape)
-            elif wt is not None:
-                # a handle and no hand-written kernel for the shape: dX = dY (W^T)^T as the NT library GEMM (the
-                # GPT-2-small LM head: 3.28 ms + 0.03 ms for wte^T against 3.83 ms for the NN form,
-                # profiles/bwd_helpers_step_kernels.txt); the caller decides by giving the handle
-                dx = mm(dy2, wt, trans_b=True).view(x.shape)
-            else:
+            route = dgrad_route(dy2.shape[0], N, K, dy2, handle=ctx.wt is not None)
+            if route == "lib_nn":
                 dx = mm(dy2, w).view(x.shape)
+            else:  # every other route reads W^T: the handle, or a transpose made here
+                dx = _gemm(route, dy2, transpose_weight(w) if ctx.wt is None else ctx.wt).view(x.shape)
         if deposit and dx is not None and not depo.ran and dx.is_contiguous():
             depo.pending, dx = dx.view(-1, K), None
         want_w = bool(ctx.needs_input_grad[1])
         want_b = bool(ctx.has_bias and ctx.needs_input_grad[2])
         bias, ctx.bias = ctx.bias, None
-        w = w_param  # gradients are formed for the parameter's own shape
-        flat_w = w.grad is not None and w.grad.is_contiguous() and w.grad.dtype == w.dtype
-        flat_b = (not want_b) or grad_buffer(bias) is not None
-        # config.async_wgrad: measured slower (951 vs 966-971 samples/s)
-        if config.get().async_wgrad and dy2.is_cuda and flat_w and flat_b and (want_w or want_b):
-            # only when every result lands in a flat .grad buffer (nothing is returned to autograd)
-            main = torch.cuda.current_stream(dy2.device)
-            side = _side_stream(dy2.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                _param_grads(dy2, x2, w, bias, want_w, want_b)
-            dy2.record_stream(side)  # keep the inputs' memory until the side stream is done with it
-            x2.record_stream(side)
-            _queue_join(main, side, dy2.device)
-            return dx, None, None, None, None, None, None
-        dw, db = _param_grads(dy2, x2, w, bias, want_w, want_b)
+        # w_param: the gradients are formed for the parameter's own shape
+        dw, db = _param_grads(dy2, x2, w_param, bias, want_w, want_b)
         return dx, dw, db, None, None, None, None
 
 
@@ -521,7 +373,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None = None,
 def dgrad_ps_ok(M: int, N: int, K: int, t) -> bool:
     """Input gradient dX[M, N] = dY[M, K] W[K, N] on gemm_ps: where it measured faster than the
     library (K <= 2304: the qkv and attention-output projections; at K = 3072 it is 3 % slower). A layer that was
-    handed W^T takes the NT library GEMM on it instead while config.dgrad_nt_attn is on (``_Linear.backward``)."""
+    handed W^T takes the NT library GEMM on it instead while config.dgrad_nt_attn is on (``dgrad_route``)."""
     return (config.get().dgrad_ps and K <= 2304 and use_native(t) and t.dtype == torch.bfloat16
             and t.is_contiguous() and bool(native().gemm_ps_supported(M, N, K, 0)))
 
@@ -537,30 +389,29 @@ class _MlpGelu(torch.autograd.Function):
     forward  fc:  one GEMM writes pre = x W1^T + b1 AND act = gelu(pre) (no bias_gelu pass);
     backward fc2-dgrad: one GEMM writes dpre = (dy W2) * gelu'(pre) and reduces db1 = sum dpre
              in its epilogue (no bias_gelu_bwd pass, dact never hits HBM).
-    `ps`: those two GEMMs run gemm_ps (persistent, nt stores; 0.81x and 0.85x the time of the library
-    GEMM + pass, profiles/r4_gemm_ps_bench.txt) and the other MLP GEMMs the library; otherwise all
+    ``mode`` 'ps': those two GEMMs run gemm_ps (persistent, nt stores; 0.81x and 0.85x the time of the library
+    GEMM + pass, profiles/r4_gemm_ps_bench.txt) and the other two what ``_mlp_routes`` names; 'nt': all
     four run the tiled gemm_nt (VCX_GEMM=vcx)."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, ps, w1t=None, w2t=None):
+    def forward(ctx, x, w1, b1, w2, mode, w1t=None, w2t=None):
         C = native()
         x2 = x.reshape(-1, x.shape[-1])
         M, F_ = x2.shape[0], w1.shape[0]
         pre = torch.empty(M, F_, device=x.device, dtype=x.dtype)
         act = torch.empty_like(pre)
-        if ps:
+        if mode == "ps":
             # `pre` holds gelu'(pre) (epilogue 5): the backward needs pre only for gelu', and the forward
             # already has sigmoid(2u) (VCX_MLP_GRAD_FWD=0: store pre, gelu' in the backward's epilogue 4)
             C.gemm_ps(x2, w1, pre, act, b1, None, 5 if config.get().mlp_grad_fwd else 2)
-            y = gemm_f(act, w2) if gemm_f_ok(M, w2.shape[0], F_, act) else mm(act, w2, trans_b=True)
         else:
             C.gemm_nt(x2, w1, pre, act, b1, None, 2)
-            y = gemm_nt(act, w2)
+        y = _gemm(_mlp_routes(mode, M, w2.shape[0], F_, act, w1t is not None)[0], act, w2)
         ctx.save_for_backward(x2, w1, b1, w2, pre, act)
         ctx.xshape = x.shape
-        ctx.ps = ps
+        ctx.mode = mode
         ctx.w1t, ctx.w2t = w1t, w2t  # from this forward's transpose_weights (kept for a second backward pass)
-        ctx.grad_fwd = bool(ps and config.get().mlp_grad_fwd)
+        ctx.grad_fwd = bool(mode == "ps" and config.get().mlp_grad_fwd)
         return y.view(*x.shape[:-1], w2.shape[0])
 
     @staticmethod
@@ -582,7 +433,7 @@ class _MlpGelu(torch.autograd.Function):
         dpre = torch.empty_like(pre)
         w1t = ctx.w1t
         w2t = transpose_weight(w2) if ctx.w2t is None else ctx.w2t
-        if ctx.ps:
+        if ctx.mode == "ps":
             C.gemm_ps(dy2, w2t, dpre, pre, None, cs, 6 if ctx.grad_fwd else 4)
         else:
             C.gemm_nt(dy2, w2t, dpre, pre, None, cs, 3)
@@ -598,14 +449,11 @@ class _MlpGelu(torch.autograd.Function):
                 db1 = cs.to(b1.dtype)
         dx = None
         if ctx.needs_input_grad[0]:
-            if not ctx.ps:
-                dx = gemm_nt(dpre, transpose_weight(w1) if w1t is None else w1t)
-            elif w1t is not None and config.get().fc_dgrad_nt:
-                # dX = dpre (W1^T)^T as the NT library GEMM: the fc2 forward's shape and kernel, 227.7 vs 251.3 us for
-                # the NN form at the GPT-2-small step (profiles/bwd_helpers_step_kernels.txt)
-                dx = mm(dpre, w1t, trans_b=True)
-            else:
+            route = _mlp_routes(ctx.mode, M, w1.shape[1], F_, dpre, w1t is not None)[1]
+            if route == "lib_nn":
                 dx = mm(dpre, w1)
+            else:
+                dx = _gemm(route, dpre, transpose_weight(w1) if w1t is None else w1t)
             dx = dx.view(ctx.xshape)
         return dx, dw1, db1, dw2, None, None, None
 
@@ -641,12 +489,23 @@ def _mlp_mode(x, w1, w2):
     return None
 
 
+def _mlp_routes(mode: str, M: int, N: int, F_: int, t, handle: bool):
+    """(fc2 forward, fc input gradient): what computes Y[M, N] = act[M, F_] W2^T and dX[M, N] = dpre[M, F_] W1 in
+    the fused MLP of ``_mlp_mode`` 'ps' or 'nt' (the names of ``forward_route`` / ``dgrad_route``; ``t``: act or
+    dpre; ``handle``: W1^T was given). The fc forward and the fc2 input gradient are the mode's epilogue GEMMs."""
+    if mode == "nt":
+        return "nt", "nt"
+    # with W1^T at hand, dX = dpre (W1^T)^T as the NT library GEMM: the fc2 forward's shape and kernel, 227.7 vs
+    # 251.3 us for the NN form at the GPT-2-small step (profiles/bwd_helpers_step_kernels.txt)
+    return ("f" if gemm_f_ok(M, N, F_, t) else "lib"), ("lib_nt" if handle and config.get().fc_dgrad_nt else "lib_nn")
+
+
 def mlp_gelu(x, w1, b1, w2, w1t=None, w2t=None):
     """gelu_tanh(x W1^T + b1) W2^T (GPT-2 MLP without the fc2 bias, which the following fused
     add + LayerNorm applies). ``w1t`` / ``w2t``: W1^T / W2^T from this forward's ``transpose_weights``."""
     mode = _mlp_mode(x, w1, w2)
     if mode is not None:
-        return _MlpGelu.apply(x, w1, b1, w2, mode == "ps", w1t, w2t)
+        return _MlpGelu.apply(x, w1, b1, w2, mode, w1t, w2t)
     from .activations import bias_gelu
 
     return linear(bias_gelu(linear(x, w1, wt=w1t), b1), w2, wt=w2t)

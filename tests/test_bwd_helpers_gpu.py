@@ -254,6 +254,73 @@ def test_linear_with_a_handle_takes_the_nt_gemm(gpu, monkeypatch):
     assert float((outs[True][1].float() - ref).norm() / ref.norm()) <= 2.0 ** -7
 
 
+# y[M, N] = x[M, K] w[N, K]^T at the smallest shape each back-end's *_supported takes (asked of the extension on the
+# CPU): gemm_nt 256 x 256 x 128, gemm_f 300 x 128 x 192, gemm_ps 256^3, the vision GEMM from 131072 rows with <= 64
+# columns and K % 32 == 0; 96 x 100 x 100 is no kernel's. An input gradient is the GEMM [M, K] = [M, N] [K, N]^T, so
+# its shapes have N and K swapped.
+_VCX, _F, _NARROW = dict(gemm="vcx"), dict(gemm_fwd="vcx"), dict(narrow_gemm="vision")
+DISPATCH = [  # direction, route, config flip, M, N, K, bias, handle
+    ("fwd", "nt", _VCX, 256, 256, 128, True, False),
+    ("fwd", "f", _F, 300, 128, 192, True, False),
+    ("fwd", "narrow", _NARROW, 131072, 64, 32, False, False),
+    ("fwd", "lib", {}, 96, 100, 100, True, False),
+    ("dgrad", "nt", _VCX, 256, 128, 256, False, False),
+    ("dgrad", "nt", _VCX, 256, 128, 256, False, True),
+    ("dgrad", "f", _F, 300, 192, 128, False, False),
+    ("dgrad", "f", _F, 300, 192, 128, False, True),
+    ("dgrad", "narrow", _NARROW, 131072, 32, 64, False, False),
+    ("dgrad", "narrow", _NARROW, 131072, 32, 64, False, True),
+    ("dgrad", "ps", {}, 256, 256, 256, True, False),
+    ("dgrad", "ps", dict(dgrad_nt_attn=False), 256, 256, 256, False, True),
+    ("dgrad", "lib_nt", {}, 256, 256, 256, False, True),  # a handle moves the gemm_ps shape to the NT library GEMM
+    ("dgrad", "lib_nt", {}, 96, 100, 100, False, True),
+    ("dgrad", "lib_nn", {}, 96, 100, 100, True, False),
+]
+
+
+@pytest.mark.parametrize("direction,route,flip,M,N,K,bias,handle", DISPATCH)
+def test_dispatch_runs_what_the_route_names(gpu, monkeypatch, transposes, direction, route, flip, M, N, K, bias, handle):
+    """One forward and backward of ops.linear with every GEMM entry point spied on: the one that ran is the one
+    forward_route / dgrad_route named (which is the one the config flip was meant to select), and the backward made
+    a transpose of its own exactly when it had no handle and its route reads W^T. The result is held to the fp32
+    product rounded to bf16 once: 2^-7 relative L2 at the worst (one bf16 ulp on every element)."""
+    ran = []
+
+    def spy(obj, name, label):
+        real = getattr(obj, name)
+
+        def wrapper(*a, **kw):
+            ran.append(label(*a, **kw) if callable(label) else label)
+            return real(*a, **kw)
+
+        monkeypatch.setattr(obj, name, wrapper)
+
+    spy(L, "gemm_nt", "nt")
+    spy(L, "gemm_f", "f")
+    spy(L, "narrow_gemm", "narrow")
+    spy(ops.native(), "gemm_ps", "ps")
+    spy(L, "mm", lambda a, b, trans_a=False, trans_b=False, bias=None: "lib_nt" if trans_b else "lib_nn")
+    g = torch.Generator(device="cpu").manual_seed(17)
+    x = torch.randn(M, K, generator=g).to(device=gpu, dtype=torch.bfloat16).requires_grad_()
+    w = (torch.randn(N, K, generator=g) * 0.05).to(device=gpu, dtype=torch.bfloat16).requires_grad_()
+    b = (torch.randn(N, generator=g) * 0.05).to(device=gpu, dtype=torch.bfloat16).requires_grad_() if bias else None
+    dy = torch.randn(M, N, generator=g).to(device=gpu, dtype=torch.bfloat16)
+    with config.override(**flip):
+        wt = ops.transpose_weights([w.detach()])[0] if handle else None
+        want_fwd, want_dgrad = L.forward_route(M, N, K, x, b), L.dgrad_route(M, N, K, dy, handle)
+        assert (want_fwd if direction == "fwd" else want_dgrad) == route
+        y = ops.linear(x, w, b, wt=wt)
+        assert ran == ["lib_nt" if want_fwd == "lib" else want_fwd] and transposes == []  # x W^T on the library is an NT GEMM
+        del ran[:]
+        y.backward(dy)
+        assert ran == [want_dgrad]
+        assert len(transposes) == (1 if not handle and want_dgrad != "lib_nn" else 0)
+    ref_y = x.detach().float() @ w.detach().float().t() + (b.detach().float() if bias else 0)
+    ref_dx = dy.float() @ w.detach().float()
+    assert float((y.detach().float() - ref_y).norm() / ref_y.norm()) <= 2.0 ** -7
+    assert float((x.grad.float() - ref_dx).norm() / ref_dx.norm()) <= 2.0 ** -7
+
+
 def test_without_preset_flat_buffers(gpu, transposes):
     """No preset .grad buffers: the gradients come back through autograd, the same with the switch on and off, and
     equal to the flat-buffer run's (one contribution per parameter, rounded to bf16 once on either route; the tied

@@ -5,9 +5,9 @@ from distributedvolunteercomputing_amd import config
 
 
 def test_from_env_parses_and_validates():
-    c = config.from_env({"VCX_GEMM": "vcx", "VCX_ASYNC_WGRAD": "1", "VCX_WGRAD_BIG_SPLIT_MIN_M": "4096",
+    c = config.from_env({"VCX_GEMM": "vcx", "VCX_WGRAD_RAGGED": "1", "VCX_WGRAD_BIG_SPLIT_MIN_M": "4096",
                          "VCX_GLOO_HOST": "10.0.0.2", "VCX_STORE_PORT": "30000"})
-    assert c.gemm == "vcx" and c.async_wgrad is True and c.wgrad_big_split_min_m == 4096
+    assert c.gemm == "vcx" and c.wgrad_ragged is True and c.wgrad_big_split_min_m == 4096
     assert c.gloo_host == "10.0.0.2" and c.store_port_train == c.store_port_video == 30000
     assert config.from_env({}) == config.RuntimeConfig()
     with pytest.raises(ValueError):

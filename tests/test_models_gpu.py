@@ -103,7 +103,7 @@ def test_resnet_bottlenecks_vs_fp32_oracle(gpu):
 
 def test_resnet_identity_shortcut_gradient_join(gpu):
     """Identity-shortcut bottlenecks (ResNet with 2 blocks per stage) take the shortcut's gradient into
-    conv1's input-gradient GEMM (ops/linear.py GradJoin, beta = 1: one rounding) instead of autograd's
+    conv1's input-gradient GEMM (ops/grad_join.py GradJoin, beta = 1: one rounding) instead of autograd's
     bf16 add; projection-shortcut blocks (stride 1 and 2) add the shortcut convolution's input gradient
     into the one conv1 deposited. Against an fp32 oracle of the same model, the joined gradients (input
     and every parameter) are no worse than the unjoined ones."""
@@ -550,7 +550,7 @@ def test_global_avgpool_and_subsample_tap_grads(gpu):
     """global_avgpool (HIP broadcast backward) and subsample_tap (HIP subsample forward, strided add backward into
     the deposited conv1 gradient) against torch autograd on the same bf16 inputs."""
     from distributedvolunteercomputing_amd.ops.batchnorm import global_avgpool
-    from distributedvolunteercomputing_amd.ops.linear import GradJoin, subsample_tap
+    from distributedvolunteercomputing_amd.ops.grad_join import GradJoin, subsample_tap
 
     torch.manual_seed(5)
     x = torch.randn(4, 64, 7, 7, device=gpu).to(torch.bfloat16).to(memory_format=torch.channels_last).requires_grad_()

@@ -1,9 +1,9 @@
-"""ops/linear.py subsample_tap: the stride-2 shortcut convolution's input and the gradient join of a
+"""ops/grad_join.py subsample_tap: the stride-2 shortcut convolution's input and the gradient join of a
 projection-shortcut ResNet block (conv1 deposits its input gradient; the tap adds the strided
 quarter into it instead of autograd's zero-filled slice gradient + full-size add)."""
 import torch
 
-from distributedvolunteercomputing_amd.ops.linear import GradJoin, subsample_tap
+from distributedvolunteercomputing_amd.ops.grad_join import GradJoin, subsample_tap
 
 
 def _x():

@@ -188,6 +188,41 @@ void q8_trimmed_reduce(at::Tensor recv, int64_t P, int64_t m, int64_t trim, int6
                         valid, out_record.data_ptr<uint8_t>(), c, nf, cur_stream());
 }
 
+// Centered clipping over the q8 records (the cclip sibling of q8_trimmed_reduce): out_record = one record of the rule
+// of ops/robust.py over the decoded rows of live_mask, `iters` updates with radius tau (0: adaptive); elements at or
+// beyond `valid` do not vote. weights: fp32 [P], nonfinite: int64 [1], both optional. The workspace (the fp32 centre,
+// the distances' chunk partials, the weights) is allocated here. Everything is checked before the launcher's own
+// checks, so a refused call leaves every output unwritten.
+void q8_cclip_reduce(at::Tensor recv, int64_t P, int64_t m, int64_t live_mask, int64_t valid, double tau, int64_t iters,
+                     at::Tensor out_record, std::optional<at::Tensor> weights, std::optional<at::Tensor> nonfinite) {
+  CHK(recv);
+  CHK(out_record);
+  TORCH_CHECK(P >= 1 && P <= 16, "q8_cclip_reduce: P must be in 1..16, got ", P);
+  TORCH_CHECK(live_mask > 0 && (live_mask >> P) == 0,
+              "q8_cclip_reduce: live_mask must name at least one of the P rows and no other, got ", live_mask);
+  TORCH_CHECK(tau >= 0.0 && tau <= 3.4028234663852886e38,  // a finite fp32 value; a NaN fails both comparisons
+              "q8_cclip_reduce: tau must be finite and >= 0 (0: adaptive), got ", tau);
+  TORCH_CHECK(iters >= 1 && iters <= 8, "q8_cclip_reduce: iters must be in 1..8, got ", iters);
+  check_q8(m, m, 1, out_record, "q8_cclip_reduce");
+  TORCH_CHECK(valid >= 0 && valid <= m, "q8_cclip_reduce: valid must be in 0..m, got ", valid);
+  TORCH_CHECK(recv.scalar_type() == at::kByte && recv.numel() >= P * (m + m / 32),
+              "q8_cclip_reduce: recv must hold P records");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(recv.data_ptr()) & 15) == 0, "q8_cclip_reduce: recv must be 16-byte aligned");
+  TORCH_CHECK(out_record.get_device() == recv.get_device(), "q8_cclip_reduce: out_record must be on recv's device");
+  if (weights)
+    TORCH_CHECK(weights->is_cuda() && weights->get_device() == recv.get_device() && weights->numel() == P &&
+                    weights->is_contiguous() && weights->scalar_type() == at::kFloat,
+                "q8_cclip_reduce: weights must hold P fp32 on recv's device");
+  if (nonfinite)
+    TORCH_CHECK(nonfinite->is_cuda() && nonfinite->get_device() == recv.get_device() && nonfinite->numel() == 1 &&
+                    nonfinite->is_contiguous() && nonfinite->scalar_type() == at::kLong,
+                "q8_cclip_reduce: nonfinite must hold 1 int64 on recv's device");
+  at::Tensor ws = at::empty({vcx_q8_cclip_workspace_floats((int)P, m)}, recv.options().dtype(at::kFloat));
+  vcx_q8_cclip_reduce(recv.data_ptr<uint8_t>(), (int)P, m, (uint32_t)live_mask, valid, (float)tau, (int)iters,
+                      out_record.data_ptr<uint8_t>(), weights ? weights->data_ptr<float>() : nullptr,
+                      nonfinite ? nonfinite->data_ptr<int64_t>() : nullptr, ws.data_ptr<float>(), cur_stream());
+}
+
 // records: P records covering L elements; out: bf16 [n], the first n decoded values
 void q8_decode(at::Tensor records, int64_t L, int64_t P, at::Tensor out) {
   CHK(records);
@@ -207,6 +242,11 @@ void vcx_register_compress(pybind11::module& m) {
         pybind11::arg("trim"), pybind11::arg("live_mask"), pybind11::arg("valid"), pybind11::arg("out_record"),
         pybind11::arg("counts") = pybind11::none(), pybind11::arg("nonfinite") = pybind11::none());
   m.def("q8_trimmed_reduce_max_blocks", &vcx_q8_trimmed_reduce_max_blocks);
+  m.def("q8_cclip_reduce", &q8_cclip_reduce, pybind11::arg("recv"), pybind11::arg("P"), pybind11::arg("m"),
+        pybind11::arg("live_mask"), pybind11::arg("valid"), pybind11::arg("tau"), pybind11::arg("iters"),
+        pybind11::arg("out_record"), pybind11::arg("weights") = pybind11::none(),
+        pybind11::arg("nonfinite") = pybind11::none());
+  m.def("q8_cclip_max_workgroups", &vcx_q8_cclip_max_workgroups);
   m.def("q8_block", &vcx_q8_block);
   m.def("topk_ef", &topk_ef);
   m.def("scatter_add", &scatter_add);

@@ -22,8 +22,10 @@
 // q8: 8-bit quantisation in blocks of 128 with one fp32 scale each and error feedback: three
 // streaming kernels (encode, reduce on the shard owner, decode), described at their section below,
 // and the robust reduce (the trimmed mean of ops/robust.py over the decoded records) that takes the
-// place of the rank-order sum under --aggregate trimmed | median.
+// place of the rank-order sum under --aggregate trimmed | median, and under --aggregate cclip (on request) the
+// centered clipping of the decoded records: an init pass, then a weights launch and a step pass per update.
 #include "robust_common.h"
+#include "vcx_api.h"
 
 namespace vcx {
 
@@ -1002,6 +1004,290 @@ __global__ void __launch_bounds__(256) q8_trimmed_reduce_kernel(const uint8_t* _
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Centered clipping over the q8 records: the cross of q8_trimmed_reduce_kernel above and the cclip kernels of
+// robust.hip. parallel/compression.py, reduce_cclip_reference, holds the definition (decode as above, then
+// ops/robust.py centered_clip_reference on the fp32 rows dec[:, :valid], then the finish of the trimmed kernel and the
+// codec); these kernels agree with it bit for bit. Over the rows named by `live` of one shard of m elements:
+//   init   v = the median rule on the decoded fp32 rows (the pairwise rank count of the trimmed kernel), kept in
+//          fp32 in the workspace, and the chunk partials of the first distances;
+//   L x    weights from the partials (cclip_weights_kernel of robust.hip, through vcx_cclip_weights), then a step:
+//          decode again, v += (sum over the rows with w > 0, ascending, of w (x - v)) * inv_K where v is finite.
+//          Not LAST: v is written back and the next partials come from the values still in registers. LAST: a
+//          non-finite v becomes +0 and is counted, elements at or beyond `valid` become +0 uncounted, and the m
+//          values are quantised into one record.
+// The work split is the q8 one and cclip's at once: a unit is 8 consecutive elements of one lane, a chunk is 512
+// units (4096 elements, 32 q8 blocks); thread t takes unit c * 512 + t, then c * 512 + 256 + t, so the 16 lanes of a
+// q8 block are the 16 aligned lanes q8_group_max exchanges among, and the thread sums of a distance are cclip's 256
+// slots. Elements at or beyond `valid` add +0 to every distance (the definition sums over `valid` elements only; a
+// distance is never -0, so the bits agree). No lane leaves a trip early: lanes past the end carry zeros to every
+// cross-lane exchange and barrier. Rows outside `live` are never read. No float atomics, no fused multiply-add.
+constexpr uint32_t Q8_CC_CHUNK_UNITS = 512;  // units of 8 elements per chunk
+constexpr int Q8_CC_MAX_BLOCKS = 2048;       // workgroup cap of the init and step passes: more chunks are strided over
+
+__device__ __forceinline__ bool q8_cc_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+
+// The 256 thread sums s[k] of one chunk -> part[k * nchunks + c] for every live row k: the xor butterfly inside a
+// wave (both lanes of a pair hold lower + higher), then (w0 + w1) + (w2 + w3).
+template <int PP>
+__device__ __forceinline__ void q8_cc_chunk_sum(float (&s)[PP], float (*wave_part)[PP], float* __restrict__ part,
+                                                uint32_t nchunks, uint32_t c, uint32_t live) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < PP; ++k) {
+    float a = s[k];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) a = a + __shfl_xor(a, o, 64);
+    if (lane == 0) wave_part[wid][k] = a;
+  }
+  __syncthreads();
+  if (threadIdx.x < PP && ((live >> threadIdx.x) & 1u)) {
+    const int k = threadIdx.x;
+    part[(int64_t)k * nchunks + c] = (wave_part[0][k] + wave_part[1][k]) + (wave_part[2][k] + wave_part[3][k]);
+  }
+  __syncthreads();  // wave_part is written again in the next chunk
+}
+
+template <int PP>
+__global__ void __launch_bounds__(256) q8_cclip_init_kernel(const uint8_t* __restrict__ recv, uint32_t bps,
+                                                             uint32_t valid, int f, int K, uint32_t live, float inv,
+                                                             float* __restrict__ v, float* __restrict__ part,
+                                                             uint32_t nchunks) {
+#pragma clang fp contract(off)
+  __shared__ float wave_part[4][PP];
+  const uint32_t units = bps * 16u;
+  const int64_t rec = (int64_t)bps * Q8_REC, soff = (int64_t)bps * Q8_BLOCK;
+  const uint32_t span = (uint32_t)(K - 1 - 2 * f);
+  for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    float s[PP];
+#pragma unroll
+    for (int k = 0; k < PP; ++k) s[k] = 0.f;
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+      const uint32_t u = c * Q8_CC_CHUNK_UNITS + h * 256u + threadIdx.x;
+      const bool in_range = u < units;
+      u32x2 w[PP];
+      float sc[PP];
+#pragma unroll
+      for (int k = 0; k < PP; ++k) {
+        w[k] = u32x2{0u, 0u};
+        sc[k] = 0.f;
+        if (in_range && ((live >> k) & 1u)) {
+          w[k] = *(const u32x2_a4*)(recv + k * rec + (int64_t)u * 8);
+          sc[k] = *(const float*)(recv + k * rec + soff + (int64_t)(u >> 4) * 4);
+        }
+      }
+      float vv[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const bool votes = in_range && u * 8u + j < valid;  // below 2^31, as m is
+        uint32_t val[PP], sk[PP], rank[PP];
+#pragma unroll
+        for (int k = 0; k < PP; ++k) {
+          const float d = q8_code(w[k][j >> 2], j & 3) * sc[k];
+          val[k] = d != d ? 0x7FC00000u : __float_as_uint(d);
+          const uint32_t flip = 0x80000000u | (((live >> k) & 1u) - 1u);  // a dead row takes the key 0xFFFFFFFF
+          sk[k] = val[k] ^ ((uint32_t)((int32_t)val[k] >> 31) | flip);
+          rank[k] = (uint32_t)(PP - 1 - k - f);  // rank - f, modulo 2^32, once the rows after k have had their say
+        }
+#pragma unroll
+        for (int k = 1; k < PP; ++k) {
+#pragma unroll
+          for (int i = 0; i < k; ++i) {
+            const uint32_t first = sk[i] <= sk[k] ? 1u : 0u;  // row i precedes row k
+            rank[k] += first;
+            rank[i] -= first;
+          }
+        }
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < PP; ++k) t += rank[k] <= span ? __uint_as_float(val[k]) : 0.f;
+        const float c0 = t * inv;  // the median rule's fp32 result: the start
+        vv[j] = c0;
+        const bool fin = votes && q8_cc_finite(c0);
+#pragma unroll
+        for (int k = 0; k < PP; ++k) {
+          const float e = fin ? __uint_as_float(val[k]) - c0 : 0.f;
+          if ((live >> k) & 1u) s[k] = s[k] + e * e;
+        }
+        // one element at a time, as in q8_trimmed_reduce_kernel: interleaved, the comparisons' lane masks spill
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (in_range) {
+        *(f32x4*)(v + (int64_t)u * 8) = f32x4{vv[0], vv[1], vv[2], vv[3]};
+        *(f32x4*)(v + (int64_t)u * 8 + 4) = f32x4{vv[4], vv[5], vv[6], vv[7]};
+      }
+    }
+    q8_cc_chunk_sum<PP>(s, wave_part, part, nchunks, c, live);
+  }
+}
+
+template <int PP, bool LAST>
+__global__ void __launch_bounds__(256) q8_cclip_step_kernel(const uint8_t* __restrict__ recv, uint32_t bps,
+                                                             uint32_t valid, int P, uint32_t live, float inv_k,
+                                                             float* __restrict__ v, const float* __restrict__ wgt,
+                                                             float* __restrict__ part, uint32_t nchunks,
+                                                             uint8_t* __restrict__ out,
+                                                             unsigned long long* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  __shared__ float wave_part[4][PP];
+  __shared__ uint32_t wave_bad[4];
+  const uint32_t units = bps * 16u;
+  const int64_t rec = (int64_t)bps * Q8_REC, soff = (int64_t)bps * Q8_BLOCK;
+  float wk[PP];
+  uint32_t use = 0u;  // live rows with a weight above zero: the others are skipped, never multiplied
+#pragma unroll
+  for (int k = 0; k < PP; ++k) {
+    wk[k] = (k < P && ((live >> k) & 1u)) ? wgt[k] : 0.f;
+    if (wk[k] > 0.f) use |= 1u << k;
+  }
+  uint32_t bad = 0;
+  for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    float s[PP];
+#pragma unroll
+    for (int k = 0; k < PP; ++k) s[k] = 0.f;
+#pragma unroll 1
+    for (int h = 0; h < 2; ++h) {
+      const uint32_t u = c * Q8_CC_CHUNK_UNITS + h * 256u + threadIdx.x;
+      const bool in_range = u < units;
+      u32x2 w[PP];
+      float sc[PP];
+#pragma unroll
+      for (int k = 0; k < PP; ++k) {
+        w[k] = u32x2{0u, 0u};
+        sc[k] = 0.f;
+        if (in_range && ((live >> k) & 1u)) {
+          w[k] = *(const u32x2_a4*)(recv + k * rec + (int64_t)u * 8);
+          sc[k] = *(const float*)(recv + k * rec + soff + (int64_t)(u >> 4) * 4);
+        }
+      }
+      float vv[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) vv[j] = 0.f;
+      if (in_range) {
+        const f32x4 v0 = *(const f32x4*)(v + (int64_t)u * 8), v1 = *(const f32x4*)(v + (int64_t)u * 8 + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          vv[j] = v0[j];
+          vv[j + 4] = v1[j];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const bool votes = in_range && u * 8u + j < valid;
+        const float c0 = vv[j];
+        float x[PP];
+#pragma unroll
+        for (int k = 0; k < PP; ++k) x[k] = q8_code(w[k][j >> 2], j & 3) * sc[k];
+        float t = 0.f;
+#pragma unroll
+        for (int k = 0; k < PP; ++k) {
+          const float term = wk[k] * (x[k] - c0);
+          t = ((use >> k) & 1u) ? t + term : t;
+        }
+        const float c1 = q8_cc_finite(c0) ? c0 + t * inv_k : c0;
+        if (LAST) {
+          const bool finite = q8_cc_finite(c1);
+          bad += (votes && !finite) ? 1u : 0u;
+          vv[j] = (votes && finite) ? c1 : 0.f;
+        } else {
+          vv[j] = c1;
+          const bool fin = votes && q8_cc_finite(c1);
+#pragma unroll
+          for (int k = 0; k < PP; ++k) {
+            const float e = fin ? x[k] - c1 : 0.f;
+            if ((live >> k) & 1u) s[k] = s[k] + e * e;
+          }
+        }
+      }
+      if (LAST) {
+        float amax = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(vv[j]));
+        amax = q8_group_max(amax);
+        float scale, dec[8];
+        const u32x2 o = q8_quantise8(vv, amax, scale, dec);
+        if (in_range) {
+          *(u32x2_a4*)(out + (int64_t)u * 8) = o;
+          if ((u & 15u) == 0) *(float*)(out + soff + (int64_t)(u >> 4) * 4) = scale;
+        }
+      } else if (in_range) {
+        *(f32x4*)(v + (int64_t)u * 8) = f32x4{vv[0], vv[1], vv[2], vv[3]};
+        *(f32x4*)(v + (int64_t)u * 8 + 4) = f32x4{vv[4], vv[5], vv[6], vv[7]};
+      }
+    }
+    if (!LAST) q8_cc_chunk_sum<PP>(s, wave_part, part, nchunks, c, live);
+  }
+  if (LAST && nonfinite) {  // registers -> wave -> block (LDS) -> one global atomic per workgroup
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    uint32_t b = bad;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) b += __shfl_xor(b, o, 64);
+    if (lane == 0) wave_bad[wid] = b;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const uint32_t tot = wave_bad[0] + wave_bad[1] + wave_bad[2] + wave_bad[3];
+      if (tot) atomicAdd(nonfinite, (unsigned long long)tot);
+    }
+  }
+}
+
+// One voter: its decoded row through the finish (non-finite -> +0, counted; at or beyond `valid` -> +0), quantised
+// again; its weight is 1, the others' 0.
+__global__ void __launch_bounds__(256) q8_cclip_one_voter_kernel(const uint8_t* __restrict__ recv, uint32_t bps,
+                                                                  uint32_t valid, int P, int row,
+                                                                  uint8_t* __restrict__ out,
+                                                                  float* __restrict__ w_user,
+                                                                  unsigned long long* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  __shared__ uint32_t wave_bad[4];
+  const uint32_t units = bps * 16u;
+  const int64_t rec = (int64_t)bps * Q8_REC, soff = (int64_t)bps * Q8_BLOCK;
+  const uint8_t* r = recv + row * rec;
+  uint32_t bad = 0;
+  for (uint32_t base = blockIdx.x * 256u; base < units; base += gridDim.x * 256u) {
+    const uint32_t u = base + threadIdx.x;
+    const bool in_range = u < units;
+    u32x2 w = {0u, 0u};
+    float sc = 0.f;
+    if (in_range) {
+      w = *(const u32x2_a4*)(r + (int64_t)u * 8);
+      sc = *(const float*)(r + soff + (int64_t)(u >> 4) * 4);
+    }
+    float res[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const bool votes = in_range && u * 8u + j < valid;
+      const float d = q8_code(w[j >> 2], j & 3) * sc;
+      const bool finite = q8_cc_finite(d);
+      bad += (votes && !finite) ? 1u : 0u;
+      res[j] = (votes && finite) ? d : 0.f;
+    }
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(res[j]));
+    amax = q8_group_max(amax);
+    float scale, dec[8];
+    const u32x2 o = q8_quantise8(res, amax, scale, dec);
+    if (!in_range) continue;
+    *(u32x2_a4*)(out + (int64_t)u * 8) = o;
+    if ((u & 15u) == 0) *(float*)(out + soff + (int64_t)(u >> 4) * 4) = scale;
+  }
+  if (w_user && blockIdx.x == 0 && (int)threadIdx.x < P) w_user[threadIdx.x] = (int)threadIdx.x == row ? 1.f : 0.f;
+  if (nonfinite) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+    if (lane == 0) wave_bad[wid] = bad;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const uint32_t tot = wave_bad[0] + wave_bad[1] + wave_bad[2] + wave_bad[3];
+      if (tot) atomicAdd(nonfinite, (unsigned long long)tot);
+    }
+  }
+}
+
 }  // namespace vcx
 
 // ====================================================================================== launchers
@@ -1149,6 +1435,67 @@ void vcx_q8_trimmed_reduce(const uint8_t* recv, int P, int64_t m, int trim, uint
 }
 
 int vcx_q8_trimmed_reduce_max_blocks() { return Q8_TRIMMED_MAX_BLOCKS; }
+
+int vcx_q8_cclip_max_workgroups() { return Q8_CC_MAX_BLOCKS; }
+
+int64_t vcx_q8_cclip_workspace_floats(int P, int64_t m) {
+  const int64_t nchunks = (m / 8 + Q8_CC_CHUNK_UNITS - 1) / Q8_CC_CHUNK_UNITS;
+  return m + (int64_t)P * nchunks + TR_MAX_P;
+}
+
+// A call the kernels cannot take raises before anything is launched.
+void vcx_q8_cclip_reduce(const uint8_t* recv, int P, int64_t m, uint32_t live_mask, int64_t valid, float tau, int iters,
+                         uint8_t* out_record, float* weights, int64_t* nonfinite, float* workspace, hipStream_t s) {
+  const std::string who = "q8_cclip_reduce";
+  check_rows(who, P, live_mask);
+  if (m <= 0 || m % Q8_BLOCK != 0 || m >= INT32_MAX)
+    throw std::invalid_argument(who + ": m must be a positive multiple of 128 below 2^31, got " + std::to_string(m));
+  if (valid < 0 || valid > m)
+    throw std::invalid_argument(who + ": valid must be in 0..m, got " + std::to_string(valid));
+  if (!(tau >= 0.f) || tau > 3.402823466e38f)
+    throw std::invalid_argument(who + ": tau must be finite and >= 0 (0: adaptive)");
+  if (iters < 1 || iters > 8)
+    throw std::invalid_argument(who + ": iters must be in 1..8, got " + std::to_string(iters));
+  if (!recv || ((uintptr_t)recv & 15)) throw std::invalid_argument(who + ": recv must be 16-byte aligned");
+  if (!out_record || ((uintptr_t)out_record & 3))
+    throw std::invalid_argument(who + ": out_record must be 4-byte aligned");
+  if ((uintptr_t)weights & 3) throw std::invalid_argument(who + ": weights must be 4-byte aligned");
+  if ((uintptr_t)nonfinite & 7) throw std::invalid_argument(who + ": nonfinite must be 8-byte aligned");
+  if (!workspace || ((uintptr_t)workspace & 15))
+    throw std::invalid_argument(who + ": workspace must be 16-byte aligned");
+  const int K = __builtin_popcount(live_mask);
+  const uint32_t bps = (uint32_t)(m / Q8_BLOCK);
+  const dim3 block(256);
+  if (K == 1) {
+    hipLaunchKernelGGL(q8_cclip_one_voter_kernel, dim3(stream_grid(m / 8, 256, Q8_CC_MAX_BLOCKS)), block, 0, s, recv,
+                       bps, (uint32_t)valid, P, __builtin_ctz(live_mask), out_record, weights,
+                       (unsigned long long*)nonfinite);
+    return;
+  }
+  const int f = trim_of(TR_MAX_P, K);  // the median rule is the start: all the trim that K voters allow
+  const float inv = trim_inv(K, f), inv_k = trim_inv(K, 0);
+  const uint32_t nchunks = (uint32_t)((m / 8 + Q8_CC_CHUNK_UNITS - 1) / Q8_CC_CHUNK_UNITS);
+  float* v = workspace;
+  float* part = v + m;
+  float* w = part + (int64_t)P * nchunks;
+  const dim3 grid(nchunks < (uint32_t)Q8_CC_MAX_BLOCKS ? nchunks : (uint32_t)Q8_CC_MAX_BLOCKS);
+  for_padded_peers(P, [&](auto pp) {
+    constexpr int PP = decltype(pp)::value;
+    hipLaunchKernelGGL(q8_cclip_init_kernel<PP>, grid, block, 0, s, recv, bps, (uint32_t)valid, f, K, live_mask, inv, v,
+                       part, nchunks);
+    for (int l = 0; l < iters; ++l) {
+      const bool last = l == iters - 1;
+      vcx_cclip_weights(part, nchunks, P, live_mask, tau, w, last ? weights : (float*)nullptr, s);
+      if (last)
+        hipLaunchKernelGGL((q8_cclip_step_kernel<PP, true>), grid, block, 0, s, recv, bps, (uint32_t)valid, P, live_mask,
+                           inv_k, v, (const float*)w, part, nchunks, out_record, (unsigned long long*)nonfinite);
+      else
+        hipLaunchKernelGGL((q8_cclip_step_kernel<PP, false>), grid, block, 0, s, recv, bps, (uint32_t)valid, P,
+                           live_mask, inv_k, v, (const float*)w, part, nchunks, out_record,
+                           (unsigned long long*)nonfinite);
+    }
+  });
+}
 
 void vcx_q8_decode(const uint8_t* records, int64_t n, int64_t L, int P, void* out_bf16, hipStream_t s) {
   const uint32_t bps = (uint32_t)(L / P / Q8_BLOCK);

@@ -391,6 +391,16 @@ void vcx_trimmed_reduce_bcast_bf16(const void* in, void* out, void* mine, int P,
 
 int vcx_cclip_max_workgroups() { return CC_MAX_BLOCKS; }
 
+// The weights launch alone: the q8 centered clipping of compress.hip writes partials of the same layout.
+void vcx_cclip_weights(const float* part, int64_t nchunks, int P, uint32_t live_mask, float tau, float* w,
+                       float* w_user, hipStream_t s) {
+  const int K = __builtin_popcount(live_mask);
+  for_padded_peers(P, [&](auto pp) {
+    hipLaunchKernelGGL(cclip_weights_kernel<decltype(pp)::value>, dim3(1), dim3(256), 0, s, part, nchunks, P, K,
+                       live_mask, tau, w, w_user);
+  });
+}
+
 int64_t vcx_cclip_workspace_floats(int P, int64_t n) {
   const int64_t nchunks = (n / 8 + CC_CHUNK_VEC - 1) / CC_CHUNK_VEC;
   return n + (int64_t)P * nchunks + TR_MAX_P;

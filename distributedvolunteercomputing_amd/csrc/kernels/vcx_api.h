@@ -78,6 +78,11 @@ void vcx_cclip_reduce_bcast_bf16(const void* in, void* out, void* mine, int P, i
                                  int iters, float* weights, float* workspace, hipStream_t s);
 int64_t vcx_cclip_workspace_floats(int P, int64_t n);
 int vcx_cclip_max_workgroups();  // workgroup cap of the passes: more chunks of 4096 elements are strided over
+// robust.hip: the weights launch of centered clipping on its own, for the q8 kernels of compress.hip, whose
+// distances' chunk partials have the same layout. part[k * nchunks + c] of every live row k -> w[P] and, where
+// given, w_user[P]: one workgroup on s. No checks: the callers have made them
+void vcx_cclip_weights(const float* part, int64_t nchunks, int P, uint32_t live_mask, float tau, float* w,
+                       float* w_user, hipStream_t s);
 
 // norm_act.hip
 void vcx_ln_fwd(const void* a, const void* b, void* xout, void* y, const void* w, const void* bias, float* mean,

@@ -37,6 +37,17 @@ void vcx_q8_reduce(const uint8_t* recv, int P, int64_t m, float avg_scale, uint8
 void vcx_q8_trimmed_reduce(const uint8_t* recv, int P, int64_t m, int trim, uint32_t live_mask, int64_t valid,
                            uint8_t* out_record, int64_t* counts, int64_t* nonfinite, hipStream_t s);
 int vcx_q8_trimmed_reduce_max_blocks();  // the launcher's grid cap (blocks of 256 lanes, 8 elements per lane)
+// recv: P records of one shard; out_record = encode(centered clipping over the rows of live_mask of the decoded
+// records): the rule of ops/robust.py on the fp32 rows, `iters` (1..8) updates with radius tau (finite, >= 0; 0:
+// adaptive), started at their median; elements at or beyond `valid` do not vote and encode as +0; a non-finite
+// result becomes +0 and adds 1 to *nonfinite. weights (P floats: the last update's) and nonfinite (1 int64) may be
+// null. workspace: vcx_q8_cclip_workspace_floats(P, m) floats, 16-byte aligned, holds no state between calls.
+// 2 iters + 1 launches on s (one with a single voter). Throws std::invalid_argument, before anything is launched,
+// for a call the kernels cannot take.
+void vcx_q8_cclip_reduce(const uint8_t* recv, int P, int64_t m, uint32_t live_mask, int64_t valid, float tau, int iters,
+                         uint8_t* out_record, float* weights, int64_t* nonfinite, float* workspace, hipStream_t s);
+int64_t vcx_q8_cclip_workspace_floats(int P, int64_t m);
+int vcx_q8_cclip_max_workgroups();  // workgroup cap of the passes: more chunks of 4096 elements are strided over
 // records: P records (L elements); writes the first n decoded values as bf16
 void vcx_q8_decode(const uint8_t* records, int64_t n, int64_t L, int P, void* out_bf16, hipStream_t s);
 int vcx_q8_block();

@@ -13,7 +13,8 @@ Trainers: localsgd (H local AdamW steps + averaging) | sharded (ZeRO-1 + buddy r
 Compression: none | topk (ratio) | powersgd (rank) | q8 (8-bit blocks, nothing to tune).
 Aggregation (localsgd): mean | trimmed (--trim) | median: the coordinate-wise trimmed mean survives peers
 that stay alive and send wrong numbers (--byzantine: fault injection for exactly that); cclip
-(--clip-tau, --clip-iters): centered clipping bounds every peer's pull on a shard in the l2 norm.
+(--clip-tau, --clip-iters): centered clipping bounds every peer's pull on a shard in the l2 norm; with
+--compression q8 it runs on the decoded 8-bit records, on request (--clip-q8).
 Optimizer state: fp32 | compact (fp8 m, fp16 v, one exponent per 32 elements; --opt-state).
 Checkpoints: utils/checkpoint.py format.
 """
@@ -146,6 +147,10 @@ def parse(argv=None):
     ap.add_argument("--clip-tau", type=float, default=0.0,
                     help="--aggregate cclip: clipping radius in the l2 norm of a shard (0: each update's median distance)")
     ap.add_argument("--clip-iters", type=int, default=3, help="--aggregate cclip: updates per round, 1..8")
+    ap.add_argument("--clip-q8", action="store_true",
+                    help="--aggregate cclip --compression q8: run centered clipping on the peers' decoded 8-bit records "
+                         "(the aggregate is quantised again; a non-finite coordinate comes out as 0 and is counted in "
+                         "nonfinite_share)")
     ap.add_argument("--ckpt-dir", default=None)
     ap.add_argument("--ckpt-every", type=int, default=0)
     ap.add_argument("--resume", action="store_true")
@@ -164,9 +169,16 @@ def parse(argv=None):
         ap.error("--clip-iters must be in 1..8")
     if not 0.0 <= a.clip_tau <= 3.4028234663852886e38:
         ap.error("--clip-tau must be finite and >= 0 (0: adaptive)")
-    if a.aggregate == "cclip" and a.compression != "none":
+    if a.clip_q8 and not (a.aggregate == "cclip" and a.compression == "q8"):
+        ap.error("--clip-q8 goes with --aggregate cclip --compression q8 and nothing else")
+    if a.aggregate == "cclip" and a.compression == "q8" and not a.clip_q8:
+        ap.error("--aggregate cclip is combined with --compression q8 only on request: add --clip-q8 (the rule then "
+                 "measures every peer's l2 distance on the decoded 8-bit records, the aggregate is quantised again, and "
+                 "a non-finite coordinate comes out as 0 and is counted in nonfinite_share)")
+    if a.aggregate == "cclip" and a.compression not in ("none", "q8"):
         ap.error(f"--aggregate cclip cannot be combined with --compression {a.compression}: the rule measures every "
-                 "peer's l2 distance on the uncompressed shard (over the q8 records it is not defined yet)")
+                 "peer's l2 distance from the centre, and top-k and PowerSGD never put the peers' own values on the "
+                 "shard owner (q8 does: --compression q8 --clip-q8)")
     if a.aggregate == "cclip" and a.algo not in (None, "direct"):
         ap.error(f"--aggregate cclip runs over the 'direct' exchange only, got --algo {a.algo}")
     return a
@@ -226,7 +238,7 @@ def main(argv=None):
                              outer_momentum=a.outer_momentum, opt_state=a.opt_state,
                              comm_dtype=torch.bfloat16 if cuda else torch.float32,
                              aggregate=a.aggregate, trim=a.trim, clip_tau=a.clip_tau, clip_iters=a.clip_iters,
-                             robust_q8=a.compression == "q8" and a.aggregate != "mean")
+                             robust_q8=a.compression == "q8" and a.aggregate != "mean", cclip_q8=a.clip_q8)
         tr = LocalSGDTrainer(model, cfg, group=group, membership=membership, device=device)
         if a.compression == "q8" and a.byzantine == "nan":
             tr.wire_hook = nan_scales
@@ -313,6 +325,8 @@ def main(argv=None):
                     rec["nonfinite_share"] = round(tr.nonfinite_share, 6)
             if getattr(out, "synced", False) and getattr(tr, "clip_weight", None) is not None:
                 rec["clip_weight"] = [round(w, 4) for w in tr.clip_weight]  # per rank, of the round just done
+                if getattr(tr, "nonfinite_share", None) is not None:  # cclip over q8 (--clip-q8)
+                    rec["nonfinite_share"] = round(tr.nonfinite_share, 6)
             t_last = now
             print(json.dumps(rec), flush=True)
             if log:

@@ -12,7 +12,8 @@
   all-reduce: all-to-all of the codes, a fused dequantise-sum-requantise on the shard owner,
   all-gather of the averaged codes. It is the one compressor that combines with the robust rules
   (``allreduce_robust``): the shard owner holds every peer's record before anything is summed, so the
-  sum becomes the coordinate-wise trimmed mean of ops/robust.py over the decoded records.
+  sum becomes the coordinate-wise trimmed mean of ops/robust.py over the decoded records, or centered clipping
+  of the decoded records (``allreduce_cclip``).
 
 All expose ``allreduce_mean(buf_bf16, group) -> averaged bf16 buffer`` so they plug into
 ``LocalSGDTrainer`` (compressing the pseudo-gradient) and the sharded data-parallel trainer
@@ -153,7 +154,8 @@ class Quant8Compressor:
     into a bf16 buffer. The second quantisation has no error feedback: its residual is at most
     half a code unit of the averaged block and identical on every peer. ``allreduce_robust`` is the
     same round with ``reduce_robust`` in the middle: the trimmed mean over the peers' decoded records
-    in place of their sum, plus one small all-reduce of the trimmed / non-finite counters.
+    in place of their sum, plus one small all-reduce of the trimmed / non-finite counters; ``allreduce_cclip``
+    has ``reduce_cclip`` there, centered clipping of the decoded records, and all-reduces the weights.
 
     Layout: the n elements are padded to L = ceil(n / (128 P)) 128 P (no padded copy is made: the
     kernels bounds-check), shard j is the elements [j m, (j + 1) m) with m = L / P, and its record
@@ -309,6 +311,78 @@ class Quant8Compressor:
         q2, s2 = q8_quantise(out.view(-1, cls.BLOCK))
         return torch.cat([q2.view(-1).view(torch.uint8), s2.view(torch.uint8)]), c, bad.sum()
 
+    def reduce_cclip(self, recv: torch.Tensor, P: int, live_mask: int | None, valid: int, tau: float, iters: int,
+                     weights: torch.Tensor | None = None, nonfinite: torch.Tensor | None = None) -> torch.Tensor:
+        """The per-peer sibling of ``reduce_robust``: one record of centered clipping (ops/robust.py) of the P
+        peers' decoded records of this peer's shard. ``reduce_cclip_reference`` holds the definition; the HIP
+        kernels (q8_cclip_*, compress.hip) match it bit for bit and run on GPU tensors, the reference elsewhere,
+        with the same refusals. `weights` (fp32 [P]) receives the last update's weights, `nonfinite` (int64 [1])
+        is added to, where given."""
+        L, m, rec = self.layout(P)
+        live_mask = robust.full_mask(P) if live_mask is None else int(live_mask)
+        robust.cclip_plan(P, live_mask, tau, iters)
+        valid = int(valid)
+        if not 0 <= valid <= m:
+            raise ValueError(f"reduce_cclip: valid must be in 0..{m}, got {valid}")
+        if recv.dtype != torch.uint8 or recv.numel() < P * rec:
+            raise ValueError(f"reduce_cclip: recv must hold {P} uint8 records of {rec} bytes")
+        for t, k, dt, what in ((weights, P, torch.float32, "weights"), (nonfinite, 1, torch.int64, "nonfinite")):
+            if t is not None and (t.dtype != dt or t.numel() != k or t.device != recv.device):
+                raise ValueError(f"reduce_cclip: {what} must hold {k} {dt} on recv's device")
+        record = self._buf(P, "record")
+        if use_native(recv):
+            native().q8_cclip_reduce(recv, P, m, live_mask, valid, float(tau), iters, record, weights, nonfinite)
+            return record
+        out, w, bad, _ = self.reduce_cclip_reference(recv[: P * rec], P, live_mask, valid, tau, iters)
+        record.copy_(out)
+        if weights is not None:
+            weights.copy_(w)
+        if nonfinite is not None:
+            nonfinite.add_(bad)
+        return record
+
+    @classmethod
+    def reduce_cclip_reference(cls, recv: torch.Tensor, P: int, live_mask: int, valid: int, tau: float, iters: int):
+        """The definition of ``reduce_cclip`` in torch, on recv's device whichever it is. recv: uint8 [P * rec], the
+        peers' records of this owner's shard of m elements. A composition of two definitions the project holds bit
+        for bit:
+
+        1. Decode, as ``reduce_robust_reference``: dec[p][i] = float(code) * scale, one fp32 multiply, on whatever
+           bytes a peer sent; a NaN product is taken as the canonical 0x7FC00000. Only dec[:, :valid] takes part.
+        2. Clip: res, w, info = ops.robust.centered_clip_reference(dec[:, :valid], live_mask, tau, iters), the
+           fp32-row rule unchanged. So the start is the median rule on fp32 rows, held in fp32; the distances are
+           summed in the documented 4096-chunk, 256-slot, pairwise-tree order over the `valid` elements; a row that
+           sends a non-finite value where the centre is finite gets weight 0; a coordinate whose centre is
+           non-finite stays frozen; with one voter that row is returned unchanged and its weight is 1.
+        3. Finish, as ``reduce_robust_reference``: a non-finite res[i] becomes +0 and adds 1 to `nonfinite`;
+           elements at or beyond `valid` are +0 and are not counted; the m values are quantised by ``q8_quantise``
+           into one record.
+
+        Returns (record uint8 [rec], w fp32 [P], nonfinite int64 scalar, info); info is that of step 2 plus
+        "result", the fp32 vector [valid] before the finish.
+
+        Two consequences. Elements beyond `valid` add +0 to every distance, and a distance never becomes -0 (it
+        is a sum of squares started at +0), so the sum over the `valid` elements here and the sum over all m
+        elements in a kernel are the same bits. And no NaN that arithmetic produces can reach an output: the
+        decode's NaN is made canonical before it is ordered; a NaN made in an update belongs either to a frozen
+        coordinate, whose update is discarded, or to a centre that overflowed, which the finish zeroes and counts
+        whatever its pattern; a NaN in a distance makes it non-finite and the weight 0 whatever its pattern. So
+        the sign and payload of such NaNs, which differ between x86 and gfx950, do not matter."""
+        rec = recv.numel() // P
+        m = rec * 32 // 33
+        valid = int(valid)
+        q, scale = cls._unpack(recv[: P * rec], P)
+        dec = (q * scale).view(P, m)[:, :valid]
+        nan = torch.tensor([0x7FC00000], dtype=torch.int32, device=recv.device).view(torch.float32)
+        dec = torch.where(torch.isnan(dec), nan, dec)
+        res, w, info = robust.centered_clip_reference(dec, live_mask, tau, iters)
+        info = dict(info, result=res)
+        bad = ~torch.isfinite(res)
+        out = torch.zeros(m, dtype=torch.float32, device=recv.device)
+        out[:valid] = torch.where(bad, torch.zeros_like(res), res)
+        q2, s2 = q8_quantise(out.view(-1, cls.BLOCK))
+        return torch.cat([q2.view(-1).view(torch.uint8), s2.view(torch.uint8)]), w, bad.sum(), info
+
     def decode_f32(self, records: torch.Tensor, P: int) -> torch.Tensor:
         """The decoded fp32 values of the P gathered records, before the bf16 output rounding
         (torch reference; the tests' view of what a round transmitted)."""
@@ -380,6 +454,33 @@ class Quant8Compressor:
             group.allreduce_(ctr)
             self.bytes_sent += 2 * (P - 1) * rec + ctr.numel() * ctr.element_size()
         return self.decode(gathered, P), ctr[:P], int(ctr[P])
+
+    def allreduce_cclip(self, g: torch.Tensor, group, tau: float, iters: int, live_ranks=None):
+        """``allreduce_robust`` with centered clipping (``reduce_cclip``) as the middle step: encode -> all-to-all
+        -> reduce_cclip -> all-gather -> one small all-reduce of the weights and the non-finite count -> decode.
+        `live_ranks`: the ranks that vote (default all). Returns (avg bf16 [n], weights fp32 [P], nonfinite int),
+        identical on every rank: per rank, the mean over the P shard owners of its last-update weight (as
+        collectives.cclip_mean_), and the coordinates whose aggregate was non-finite and came out as 0."""
+        P, r = (1, 0) if group is None else (group.size, group.rank)
+        mask = robust.mask_of(live_ranks, P)
+        robust.cclip_plan(P, mask, tau, iters)  # every refusal before e is touched
+        L, m, rec = self.layout(P)
+        valid = min(max(self.n - r * m, 0), m)
+        wire = self.encode(g, P)
+        w = torch.zeros(P, dtype=torch.float32, device=self.device)
+        bad = torch.zeros(1, dtype=torch.int64, device=self.device)
+        if P == 1:
+            gathered = self.reduce_cclip(wire, 1, mask, valid, tau, iters, w, bad)
+            return self.decode(gathered, 1), w, int(bad)
+        recv, gathered = self._buf(P, "recv"), self._buf(P, "gathered")
+        group.alltoall_(recv, wire, [rec] * P, [rec] * P)
+        record = self.reduce_cclip(recv, P, mask, valid, tau, iters, w, bad)
+        group.all_gather_(gathered, record)
+        # one collective for both: fp64 holds the fp32 weights and a count below 2^53 exactly
+        side = torch.cat([w.double(), bad.double()]).to(group.device if group.backend == "nccl" else "cpu")
+        group.allreduce_(side)
+        self.bytes_sent += 2 * (P - 1) * rec + side.numel() * side.element_size()
+        return self.decode(gathered, P), (side[:P] / P).float(), int(side[P])
 
 
 class PowerSGDCompressor:

@@ -16,7 +16,9 @@ q8 shard owner holds every peer's record of its shard before anything is summed,
 the trimmed mean of the decoded records instead (Quant8Compressor.allreduce_robust).
 ``aggregate="cclip"`` is the per-peer rule over the same exchange (collectives.cclip_mean_): every shard owner
 clips the peers' copies of its shard around their median, so one peer moves a shard's aggregate by at most
-clip_iters * tau / K in l2 whatever it sends. It runs uncompressed, over `direct`, in this trainer only.
+clip_iters * tau / K in l2 whatever it sends. It runs over `direct`, in this trainer only: uncompressed, or (on
+request: LocalSGDConfig.cclip_q8) over the q8 exchange, where the shard owner clips the peers' decoded records and
+quantises the aggregate again (Quant8Compressor.allreduce_cclip).
 
 Reference analog: the chunk (100 frames) is the reference's unit of independent work
 (worker.py:16, server.py:77-91); here the unit is H optimizer steps.
@@ -72,6 +74,13 @@ class LocalSGDConfig:
     # non-finite comes out as 0 and is counted in nonfinite_share where the uncompressed rule hands on the NaN),
     # so the caller says that this is what it wants. `train --compression q8 --aggregate ...` says so
     robust_q8: bool = False
+    # let centered clipping run over the q8 exchange (Quant8Compressor.allreduce_cclip). Off by default, so cclip with
+    # any compressor is refused as before: over q8 the rule measures the peers' distances on their decoded 8-bit
+    # records, the aggregate is quantised again, and a coordinate whose aggregate is non-finite (a non-finite centre:
+    # more than half the voters sent one there) comes out as 0 and is counted in nonfinite_share where the
+    # uncompressed rule hands on the NaN, so the caller says that this is what it wants. `train --aggregate cclip
+    # --compression q8 --clip-q8` says so
+    cclip_q8: bool = False
 
     def __post_init__(self):
         check_aggregate(self.aggregate, self.trim, self.clip_tau, self.clip_iters)
@@ -115,7 +124,7 @@ class LocalSGDTrainer:
         self.wire_hook = None
         self.trim_share = None  # robust rules: per rank, the share of its elements trimmed in the last round
         # robust rules over q8: the share of the coordinates whose aggregate was non-finite (more than `trim`
-        # bad voters, or an overflowing sum) and came out as 0 in the last round
+        # bad voters, or an overflowing sum; under cclip a non-finite centre) and came out as 0 in the last round
         self.nonfinite_share = None
         # cclip: per rank, its weight in the last round's last update (the mean over the shard owners); 1 = never
         # clipped, 0 = ignored. None under the other rules
@@ -295,18 +304,21 @@ class LocalSGDTrainer:
         robust = c.aggregate != "mean"
         if robust:
             check_aggregate(c.aggregate, c.trim, c.clip_tau, c.clip_iters)
-            if c.aggregate == "cclip" and self.compressor is not None:
+            clip_q8 = c.aggregate == "cclip" and c.cclip_q8 and isinstance(self.compressor, Quant8Compressor)
+            if c.aggregate == "cclip" and self.compressor is not None and not clip_q8:
                 raise ValueError(f"aggregate='cclip' cannot be combined with the {type(self.compressor).__name__} "
-                                 "compressor: the rule measures every peer's l2 distance from the centre on the "
-                                 "uncompressed shard; top-k and PowerSGD never put the peers' own values on the "
-                                 "shard owner, and over the q8 records the rule is not defined yet")
+                                 "compressor: the rule measures every peer's l2 distance from the centre; top-k and "
+                                 "PowerSGD never put the peers' own values on the shard owner, and over the q8 "
+                                 "records the rule runs only on request: set LocalSGDConfig.cclip_q8 with a "
+                                 "Quant8Compressor (the aggregate is then quantised again, and a non-finite "
+                                 "coordinate comes out as 0 and is counted in nonfinite_share)")
             if self.compressor is not None and not isinstance(self.compressor, Quant8Compressor):
                 raise ValueError(f"aggregate={c.aggregate!r} cannot be combined with the "
                                  f"{type(self.compressor).__name__} compressor: a coordinate-wise rule needs every "
                                  "peer's own value of every coordinate on the shard owner, and top-k sends a "
                                  "different set of coordinates from every peer while PowerSGD sums low-rank "
                                  "factors; q8 is the compressor that works with the robust rules")
-            if self.compressor is not None and not c.robust_q8:
+            if self.compressor is not None and not c.robust_q8 and not clip_q8:
                 raise ValueError(f"aggregate={c.aggregate!r} is combined with the q8 compressor only on request: set "
                                  "LocalSGDConfig.robust_q8 (the rule then runs on the peers' decoded 8-bit records: "
                                  "the aggregate is quantised again, and a non-finite coordinate comes out as 0 and "
@@ -357,6 +369,11 @@ class LocalSGDTrainer:
         c = self.cfg
         live = self._voters(g, newcomers)
         K = g.size if live is None else len(live)
+        if c.aggregate == "cclip" and self.compressor is not None:  # q8 with cclip_q8: anything else was refused
+            avg, w, nonfinite = self.compressor.allreduce_cclip(self.delta, g, c.clip_tau, c.clip_iters, live)
+            self.clip_weight = w.tolist()
+            self.nonfinite_share = nonfinite / self.delta.numel()
+            return avg, 1.0
         if c.aggregate == "cclip":
             with self._timed_reduce():
                 w = cclip_mean_(self.delta, g, c.clip_tau, c.clip_iters, live)
